@@ -13,10 +13,16 @@ ranks itself (torch.distributed.run, as a child process) when it is not
 already running under a launcher.  Each step is one full view on every rank;
 view i's all-gather runs behind view i+1's kernels, and the last view's
 gather completes inside the timed region.  The headline gathers fp32 (exact);
-the lossy q16 transport is timed after it and reported beside it.
+with --full the lossy q16 transport is timed after it and reported beside it.
 
 Prints ONE JSON line (rank 0).  `value` = rays of the whole view x steps /
-(max over ranks of the timed region).  `roofline` prices the dominant kernel
+(max over ranks of the timed region); `ms_per_step` = that region / steps.
+A plain run sets up, warms up (tuning the views in flight), times the steps,
+writes the last timed view's outputs with --dump-outputs DIR and prints the
+line.  Everything below -- stage times and rooflines, the side measurements,
+the reference-equivalent and CPU baselines, the parity comparison -- takes
+runs of its own and is measured only with --full, which adds it to the same
+line.  `roofline` prices the dominant kernel
 against the guide peak of the unit closest to saturation (L2 bandwidth on the
 algorithmic bytes, VALU issue or MFMA issue) from HIP events
 recorded on the launch stream, with the per-ray counter rates of the
@@ -96,18 +102,28 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--H", type=int, default=512)
     ap.add_argument("--W", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="--mode render: after the headline also measure what takes runs of its own: "
+                         "per-stage times and rooflines, the side measurements (--no-alt skips them), "
+                         "the reference-equivalent GPU baseline (--ref-gpu-rays), the CPU baseline and "
+                         "the parity comparison (--cpu-rays); without it only the headline is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode render: after the timed steps write the last timed view's outputs "
+                         "(what a caller of the render receives: image, depth, weights_sum, samvit) "
+                         "as DIR/<name>.npy in float32, rows in ray order; an output above 32 MiB is "
+                         "written as a fixed sample of its rows (dump_outputs)")
     ap.add_argument("--no-sam", action="store_true", help="config 2 (RGB only)")
     ap.add_argument("--cpu-rays", type=int, default=262144,
-                    help="rays in the CPU-baseline sample (0 = skip)")
+                    help="--full: rays in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--ref-gpu-rays", type=int, default=262144,
-                    help="rays of the view rendered by run_torch, the reference's unfused op "
+                    help="--full: rays of the view rendered by run_torch, the reference's unfused op "
                          "sequence on the same GPU (0 = skip)")
     ap.add_argument("--head-mode", type=int, default=0,
                     help="0 = f16x3 (fp32-equivalent) grid_mlp + SAM / mask heads (default), "
                          "1 = exact fp32 MFMA")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the side measurements after the headline (exact-fp32 precision at "
-                         "N=1, q16 transport at N>1)")
+                    help="--full: skip the side measurements after the headline (exact-fp32 precision "
+                         "at N=1, q16 transport at N>1)")
     ap.add_argument("--chunks", type=int, default=0,
                     help="N > 1: 0 = one launch per view with its all-gather pipelined behind "
                          "the next view's rendering; k > 0 = k row chunks per view, each "
@@ -1000,8 +1016,32 @@ def stage_clocks():
         return None
 
 
+DUMP_MAX_BYTES = 32 << 20      # per output; the four of a SAM view come to ~37 MB
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the last timed view's outputs (the dict a caller of the
+    render receives) as path/<name>.npy, float32, rows in ray order.  An
+    output above DUMP_MAX_BYTES (samvit: 256 floats per ray) is written as a
+    sample of its rows: DUMP_MAX_BYTES / row bytes of them, drawn without
+    replacement by numpy's default_rng(0) and sorted, so the same rows in
+    every run and every build."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        if not torch.is_tensor(v) or not v.is_floating_point():
+            continue
+        a = v.detach().to(torch.float32)
+        if a.numel() * 4 > DUMP_MAX_BYTES:
+            n_keep = DUMP_MAX_BYTES // (4 * a[0].numel())
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], n_keep, replace=False))
+            a = a[torch.from_numpy(keep).to(a.device)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a.cpu().numpy()))
+
+
 def main():
     args = parse()
+    if args.dump_outputs and args.mode != "render":
+        raise SystemExit("bench.py: --dump-outputs covers --mode render (the flagship workload)")
     rc = maybe_launch(args)
     if rc is not None:
         sys.exit(rc)
@@ -1032,16 +1072,23 @@ def main():
     band_rays = (r1 - r0) * W
     codec = args.gather_codec
 
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("bench.py: --dump-outputs writes the last timed view: --steps must be >= 1")
     runner = ViewRunner(args, renderer, world, dev, H, W, pose, intr, r0, r1, codec)
-    dt, last, stage_avg, stage_src = runner.run(args.steps, args.warmup)
+    dt, last, stage_avg, stage_src = runner.run(args.steps, args.warmup, stages=args.full)
     value = n_total * args.steps / dt
-    roof, stage_roof = rooflines(stage_avg, band_rays, args.head_mode, pmc_rates(), stage_clocks(),
-                                 runner.clock)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    # what takes runs of its own: only with --full
+    alt = args.full and not args.no_alt
+    if args.full:
+        roof, stage_roof = rooflines(stage_avg, band_rays, args.head_mode, pmc_rates(), stage_clocks(),
+                                     runner.clock)
 
     side = {}
-    if world > 1 and args.chunks == 0 and codec == "fp32":
+    if args.full and world > 1 and args.chunks == 0 and codec == "fp32":
         side["gather_explained"] = explain_gather(runner)
-    if not args.no_alt and world > 1 and with_sam and args.chunks == 0:
+    if alt and world > 1 and with_sam and args.chunks == 0:
         # the other transport, same views, after the headline
         other = "q16" if codec == "fp32" else "fp32"
         r2 = ViewRunner(args, renderer, world, dev, H, W, pose, intr, r0, r1, other)
@@ -1056,7 +1103,7 @@ def main():
             "what": "q16: 536 B/ray transport, samvit int16 x per-ray power-of-two scale, |err| <= "
                     "2^-14 of the ray's max |samvit|, own band fp32" if other == "q16" else
                     "fp32: 1,044 B/ray exact transport"}
-    if not args.no_alt and world == 1 and args.rank_share <= 1:
+    if alt and world == 1 and args.rank_share <= 1:
         # the other precision mode on the same view (DTYPE)
         other = 1 - args.head_mode
         r3 = ViewRunner(args, FusedRenderer(net, head_mode=other), 1, dev, H, W, pose, intr, r0, r1, codec)
@@ -1068,7 +1115,7 @@ def main():
             if with_sam else None,
             "max_abs_image_vs_headline": float((last3["image"] - last["image"]).abs().max())}
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1:
+    if alt and world == 1 and args.rank_share <= 1:
         # N1, the flagged non-parity early exit (samnerf_model.t_thresh), on a
         # scene whose rays saturate (random weights never do); timed against
         # the default mode on the same scene and view
@@ -1107,7 +1154,7 @@ def main():
                     "mode is reported above and, where exceeds_1e-3_bar is true, breaks the "
                     "north star's 1e-3 feature bar"}
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1 and with_sam:
+    if alt and world == 1 and args.rank_share <= 1 and with_sam:
         # BASELINE config 2 (512x512 RGB only; renderer.py:221-362 without the
         # SAM branch) on the same view: its own model, the fused path and the
         # reference's op sequence on the same GPU
@@ -1136,7 +1183,7 @@ def main():
                     "skipped, return_feats=0) + 64x64 rays with 256-d SAM features; readme.md:5 quotes "
                     "5 FPS on a V100 for this loop including the SAM decoder (not run here)"}
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1:
+    if alt and world == 1 and args.rank_share <= 1:
         # perturb=True (renderer.py:266-271, :100-101: the distillation step's
         # teacher render, the GUI's spp > 1) on the fused kernels, the torch
         # draws of the perturbed positions inside the timed region
@@ -1158,11 +1205,11 @@ def main():
                     "stage-0 bins and sample_pdf positions (fused.perturbed_positions) + the fused "
                     "render fed them (samnerf_model.perturb), one stream"}
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1:
+    if alt and world == 1 and args.rank_share <= 1:
         # the --with_mask instance head on the fused kernels
         side["mask_default_head"] = mask_view(dev, max(3, args.steps // 2), 2, args.head_mode)
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1 and with_sam:
+    if alt and world == 1 and args.rank_share <= 1 and with_sam:
         # BASELINE config 5 beside the headline (`--mode train` runs it alone)
         ms5, loss5 = train_steps(dev, 20, 5)
         ms5d, loss5d = train_steps(dev, 20, 5, deterministic=True)
@@ -1175,7 +1222,7 @@ def main():
                                           "(samnerf_sgrid_backward_det, SURVEY H5): gradients repeat bit for "
                                           "bit (tests/test_gpu_train.py::test_distillation_steps_repeat_bit_for_bit)"}}
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1:
+    if alt and world == 1 and args.rank_share <= 1:
         # the reference's RGB training stage on the HIP training
         # kernels, the torch path beside it
         msr, lossr = rgb_train_steps(dev, 20, 5, fused=True)
@@ -1185,7 +1232,7 @@ def main():
                              "torch_path_ms_per_step": msr_t, "speedup_vs_torch_path": msr_t / msr,
                              **RGB_TRAIN_WHAT}
 
-    if not args.no_alt and world == 1 and args.rank_share <= 1:
+    if alt and world == 1 and args.rank_share <= 1:
         # the --with_mask training step on the HIP mask-training
         # kernels, the torch path beside it
         msm, lossm = mask_train_steps(dev, 20, 5, fused=True)
@@ -1238,18 +1285,17 @@ def main():
                                                     if codec == "q16" else " (1,044 B/ray, exact)")}
                           if world > 1 and args.chunks == 0 else {})},
             "timed_clock": runner.clock,
-            "stage_ms_source": stage_src,
-            "roofline": roof,
-            "stage_ms": stage_avg,
-            "stage_roofline": stage_roof,
+            "full": args.full,
+            **({"stage_ms_source": stage_src, "roofline": roof, "stage_ms": stage_avg,
+                "stage_roofline": stage_roof} if args.full else {}),
             **side,
         }
-        if world == 1 and args.ref_gpu_rays > 0:
+        if args.full and world == 1 and args.ref_gpu_rays > 0:
             ro_all, rd_all = ops.get_rays(pose, intr, H, W, device=dev)
             ref = reference_equivalent_gpu(net, ro_all, rd_all, args.ref_gpu_rays)
             ref["speedup"] = value / ref["value"]
             rec["reference_equivalent_gpu"] = ref
-        if world == 1 and args.cpu_rays > 0:
+        if args.full and world == 1 and args.cpu_rays > 0:
             # parity weights (embeddings U(+-0.5)): a non-trivial
             # scene for the PSNR / max-error comparison; the same view
             pnet, pspec, pparams = build_net(with_sam, dev, seed=33, emb_scale=0.5)

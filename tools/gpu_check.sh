@@ -17,11 +17,11 @@ if [ "${RUN_TA:-0}" = "1" ]; then
 timeout -k 10 120 tools/bin/ta_rate > "$OUT/ta_rate.json" 2> "$OUT/ta_rate.err"; rc=$?; echo "ta_rate rc=$rc"; cat "$OUT/ta_rate.json"; stop_if_fatal $rc ta_rate
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1; rc=$?; echo "bench rc=$rc"; tail -2 "$OUT/bench.log"; stop_if_fatal $rc bench
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1; rc=$?; echo "bench rc=$rc"; tail -2 "$OUT/bench.log"; stop_if_fatal $rc bench
 fi
 # per-rank loads of an N-GPU strong-scaled 512x512 view: H = 512/N rows
 for h in ${SWEEP_H:-}; do
-timeout -k 10 200 python bench.py --H $h --cpu-rays 0 --steps 20 > "$OUT/bench_h$h.log" 2>&1; rc=$?; echo "bench H=$h rc=$rc"; tail -1 "$OUT/bench_h$h.log" | python -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['ms_per_step'], {k: round(v,3) for k,v in r['stage_ms'].items()})"; stop_if_fatal $rc bench_h$h
+timeout -k 10 200 python bench.py --full --H $h --cpu-rays 0 --steps 20 > "$OUT/bench_h$h.log" 2>&1; rc=$?; echo "bench H=$h rc=$rc"; tail -1 "$OUT/bench_h$h.log" | python -c "import json,sys; r=json.loads(sys.stdin.read()); print(r['value'], r['ms_per_step'], {k: round(v,3) for k,v in r['stage_ms'].items()})"; stop_if_fatal $rc bench_h$h
 done
 if [ "${SKIP_PROF:-0}" != "1" ]; then
 cd /tmp && export TMPDIR=/tmp
