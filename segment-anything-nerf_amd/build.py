@@ -26,6 +26,7 @@ DIAG_LIB = os.path.join(OUT_DIR, "libsamnerf_hip_diag.so")
 DIAG_OBJ_DIR = os.path.join(HERE, "build", "obj_diag")
 
 SOURCES = ["common.cpp", "grid_encoder.hip", "sh_freq_encoder.hip", "raymarch.hip",
+           "prop_stages.hip", "final_stage.hip", "sgrid.hip",
            "sam_head.hip", "tile_codec.hip", "train_optim.hip", "sam_head_train.hip",
            "mask_head.hip", "rgb_train.hip", "mask_head_train.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -58,6 +59,17 @@ def _compile(src, diag=False):
     return obj
 
 
+def _reads_diag_switch(src):
+    """Whether -DSAMNERF_DIAG_VARIANTS can change src's object: src, or a
+    header beside it, names the switch or reads it through diag_env
+    (samnerf_common.h only defines diag_env).  The diagnostic library links the
+    product object of a source that does not -- half of them, the grid encoder's
+    long compile among them."""
+    files = [src] + [h for h in os.listdir(CSRC) if h.endswith(".h") and h != "samnerf_common.h"]
+    return any(t in open(os.path.join(CSRC, f)).read() for f in files
+               for t in ("SAMNERF_DIAG_VARIANTS", "diag_env"))
+
+
 def _link(objs, lib):
     if not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
@@ -67,21 +79,26 @@ def _link(objs, lib):
 
 
 ASM_DIR = os.path.join(HERE, "build", "asm")
+DIAG_ASM_DIR = os.path.join(HERE, "build", "asm_diag")
 
 
-def build_asm(jobs=None, sources=None):
+def build_asm(jobs=None, sources=None, diag=False):
     """Device assembly (hipcc --cuda-device-only -S, the product flags) of
     every product source into build/asm/<src>.s, rebuilt when older than its
     inputs: the input of the inline-asm hazard lint (tools/isa_hazards.py,
     tests/test_isa_hazards.py), which needs the ;;#ASMSTART / ;;#ASMEND
-    markers a disassembly does not carry."""
-    os.makedirs(ASM_DIR, exist_ok=True)
+    markers a disassembly does not carry.  diag=True: the diagnostic build's
+    (-DSAMNERF_DIAG_VARIANTS) into build/asm_diag; tools/isa_diff.py compares
+    two such directories kernel by kernel."""
+    asm_dir = DIAG_ASM_DIR if diag else ASM_DIR
+    os.makedirs(asm_dir, exist_ok=True)
     srcs = [s for s in (sources or SOURCES) if s.endswith(".hip")]
+    flags = FLAGS + (["-DSAMNERF_DIAG_VARIANTS"] if diag else [])
 
     def one(src):
-        out = os.path.join(ASM_DIR, src + ".s")
+        out = os.path.join(asm_dir, src + ".s")
         if _newer(os.path.join(CSRC, src), out):
-            cmd = [HIPCC] + FLAGS + ["--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out]
+            cmd = [HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out]
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError(f"hipcc -S failed on {src}:\n{r.stderr}")
@@ -96,12 +113,16 @@ def build(jobs=None, verbose=True, diag=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     os.makedirs(DIAG_OBJ_DIR, exist_ok=True)
     jobs = jobs or min(2 * len(SOURCES), os.cpu_count() or 4, 8)
-    work = [(src, False) for src in SOURCES] + ([(src, True) for src in SOURCES] if diag else [])
+    own = [src for src in SOURCES if diag and _reads_diag_switch(src)]
+    # the diagnostic objects first: sam_head.hip's (its variant forms) takes
+    # about three times as long as any other object, so it bounds the build
+    # and has to start at once
+    work = [(src, True) for src in own] + [(src, False) for src in SOURCES]
     with cf.ThreadPoolExecutor(jobs) as ex:
-        objs = list(ex.map(lambda a: _compile(*a), work))
-    _link(objs[:len(SOURCES)], LIB)
+        objs = dict(zip(work, ex.map(lambda a: _compile(*a), work)))
+    _link([objs[src, False] for src in SOURCES], LIB)
     if diag:
-        _link(objs[len(SOURCES):], DIAG_LIB)
+        _link([objs[src, src in own] for src in SOURCES], DIAG_LIB)
     if verbose:
         print(f"[samnerf] built {LIB}" + (f" and {os.path.basename(DIAG_LIB)}" if diag else ""))
     return LIB

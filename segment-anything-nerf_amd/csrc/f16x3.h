@@ -36,8 +36,8 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 // Power-of-two scale s and its inverse for a column (or row) whose largest
 // magnitude is `maxabs` (>= 0): maxabs * s in [2^13, 2^14) -- one binade below
 // fp16's top, so values up to 4x the maximum a scale was chosen for still fit
-// (the headroom k_final's one-block-at-a-time layer 1, SAMNERF_FINAL_JOINT = 0,
-// relies on; the default joint form takes one scale over both k-blocks).  The exponent is
+// (the headroom k_final's former one-block-at-a-time layer 1 relied on; its
+// joint scale is one scale over both k-blocks).  The exponent is
 // clamped so that both s and 1/s are normal floats (all-zero or tiny columns
 // get s = 2^125; inf / NaN columns s = 2^-115 and stay inf / NaN).
 struct Scale2 {

@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "f16x3.h"
+#include "heads.h"
 #include "samnerf_common.h"
 
 using namespace samnerf;

@@ -38,6 +38,7 @@
 
 #include "f16x3.h"
 #include "fp32_chain.h"
+#include "heads.h"
 #include "samnerf_common.h"
 
 using namespace samnerf;
@@ -703,7 +704,7 @@ int mask_weights(const samnerf_model* m, MaskW& mw) {
 //               bitwise reproducible, no atomics).
 // fp32 VALU fma chains (4,096 rays x ~60 K MACs: the render dominates).
 constexpr int kAdU = 96;                      // hidden width (network.py:147 mask_mlp_dim)
-constexpr int kAdX = 240;                     // X row (raymarch.hip kAeff)
+constexpr int kAdX = 240;                     // X row (render_args.h kAeff)
 constexpr int kAdRays = 16;                   // rays per workgroup (fwd / bwd)
 constexpr int kAdMaxL = 8;
 

@@ -10,7 +10,7 @@
 // MSE / entropy terms in one call).
 //
 // Forward
-//   proposal stages     the fused render's own kernels (raymarch.hip
+//   proposal stages     the fused render's own kernels (prop_stages.hip
 //                       proposal_forward): ds, weights and bins of both stages
 //   k_rt_final_fwd      one thread per final sample (ray-major): bins ->
 //                       position -> contract -> grid L16C2 gather (packed /
@@ -63,7 +63,7 @@ constexpr int kG0 = 64 * 32, kG1 = 64 * 64, kG2 = 16 * 64; // grid_mlp [64,32] [
 constexpr int kGW = kG0 + kG1 + kG2;
 
 // torch.linspace(start, end, steps) on the CPU (samnerf_linspace_host; the
-// same formula as raymarch.hip's stage-0 bins)
+// same formula as render_args.h's Lin, the stage-0 bins)
 struct LinSpace {
     float start, end, step;
     uint32_t steps;

@@ -18,6 +18,7 @@
 //     from L2.
 #include "samnerf_common.h"
 #include "f16x3.h"
+#include "heads.h"
 
 namespace samnerf {
 

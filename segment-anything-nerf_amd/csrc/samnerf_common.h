@@ -70,8 +70,9 @@ struct GridDesc {
 };
 
 // What the RGB training step (rgb_train.hip) takes from the fused render
-// (raymarch.hip): the model's grids resolved as the render resolves them, the
-// grid-space scale, and the proposal stages run by the render's own kernels
+// (raymarch.hip, prop_stages.hip): the model's grids resolved as the render
+// resolves them, the grid-space scale, and the proposal stages run by the
+// render's own kernels
 // with their intermediates written to the caller's buffers (sample-major
 // [k][N], ray order).
 struct TrainGeometry {

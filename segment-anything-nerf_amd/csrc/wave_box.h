@@ -14,7 +14,7 @@
 //      LDS slice and every lane reads its 8 corners from LDS; a bigger box
 //      takes the direct gathers.
 // Rows, weights and FMA order are lookup_level3's, so results are
-// bit-identical to the direct path (k_sgrid_box4 in raymarch.hip).  A lane whose corners fall outside the
+// bit-identical to the direct path (k_sgrid_box4 in sgrid.hip).  A lane whose corners fall outside the
 // box anyway (a NaN position clamps to cell 0, and fminf/fmaxf skip NaN in
 // the range) gathers directly.
 #pragma once

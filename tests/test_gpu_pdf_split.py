@@ -1,4 +1,4 @@
-"""k_prop_pdf's split phase A (raymarch.hip prop_pdf_phases, SAMNERF_PDF_SPLIT,
+"""k_prop_pdf's split phase A (prop_stages.hip prop_pdf_phases, SAMNERF_PDF_SPLIT,
 round 6): the two double cumulative sums of the proposal pdf
 (nerf/renderer.py:84-119 sample_pdf's cdf, :310-326 compositing's
 transmittance) run as quarter prefix sums over the block's four waves when

@@ -354,7 +354,7 @@ def test_exact_fp32_mode_vs_oracle(hip_lib, cuda):
 @pytest.mark.parametrize("small", ["hashed", "dense"])
 def test_final_joint_scale_over_wide_level_ranges(hip_lib, cuda, small):
     """k_final's layer 1 takes ONE f16x3 scale over both k-blocks
-    (all 16 levels, SAMNERF_FINAL_JOINT), so a level far below the column's
+    (all 16 levels, the joint scale), so a level far below the column's
     max keeps fewer bits in its fp16 halves.  With the hashed (or the dense)
     levels' embeddings 2^-20 of the others, the default form still sits at
     fp32 rounding against the oracle and the exact-fp32 form, as at equal

@@ -106,3 +106,14 @@ def test_ray_of_slots_matches_ray_tiles():
         assert int(m[s]) == (trow * 4 + inn // 8) * W + tcol * 8 + inn % 8
     assert torch.equal(ray_of_slots(W * H - W, W), torch.arange(W * H - W))   # not 4 whole rows
     assert torch.equal(ray_of_slots(100, 0), torch.arange(100))
+
+
+def test_build_sources_list_every_csrc_file():
+    """build.SOURCES is the one list of what goes into the library (tools/
+    build_ab.sh takes it from there): every csrc/*.hip and csrc/*.cpp is in
+    it, so a new file cannot silently stay out, and every entry exists."""
+    import os
+    import build
+    on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp")))
+    assert sorted(build.SOURCES) == on_disk
+    assert len(set(build.SOURCES)) == len(build.SOURCES)

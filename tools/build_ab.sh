@@ -9,7 +9,8 @@ mkdir -p $OUT
 SRC=segment-anything-nerf_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -I include $*"
 pids=()
-for f in common.cpp grid_encoder.hip sh_freq_encoder.hip raymarch.hip sam_head.hip tile_codec.hip train_optim.hip sam_head_train.hip mask_head.hip rgb_train.hip mask_head_train.hip; do
+# the one source list: build.py's
+for f in $(cd segment-anything-nerf_amd && python -c "import build; print(*build.SOURCES)"); do
   if [ "${f##*.}" = cpp ]; then X="-x hip"; else X=""; fi
   hipcc $X $FLAGS -c $SRC/$f -o $OUT/$f.o &
   pids+=($!)

@@ -3,9 +3,9 @@
 
 usage:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -munsafe-fp-atomics \
-        -I include --cuda-device-only -S -o /tmp/raymarch.s \
-        segment-anything-nerf_amd/csrc/raymarch.hip
-  python tools/isa_stats.py /tmp/raymarch.s [name-filter]
+        -I include --cuda-device-only -S -o /tmp/final_stage.s \
+        segment-anything-nerf_amd/csrc/final_stage.hip
+  python tools/isa_stats.py /tmp/final_stage.s [name-filter]
 
 Counts are of the straight-line text (loop bodies once), a proxy for the
 VALU issue cost per thread of the march kernels, which are mostly

@@ -22,7 +22,7 @@ Cycles price each VALU instruction at its measured issue cost per wave64
 v_exp / v_rcp / v_fma_mix, 4.1 the rest.
 
 usage:
-  python tools/prop_budget.py segment-anything-nerf_amd/build/asm/raymarch.hip.s
+  python tools/prop_budget.py segment-anything-nerf_amd/build/asm/prop_stages.hip.s
 (build.py build_asm writes that file; tests/test_isa_hazards.py builds it)"""
 import collections
 import re

@@ -3,8 +3,8 @@
 
 usage:
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -munsafe-fp-atomics \\
-        -I include --cuda-device-only -S -o /tmp/raymarch.s segment-anything-nerf_amd/csrc/raymarch.hip
-  python tools/valu_budget.py /tmp/raymarch.s [mangled-kernel-name]
+        -I include --cuda-device-only -S -o /tmp/final_stage.s segment-anything-nerf_amd/csrc/final_stage.hip
+  python tools/valu_budget.py /tmp/final_stage.s [mangled-kernel-name]
 
 The product kernel's sample loop is straight-line code (LAY 1: the level
 classes are compile-time constants), so a static count of its body is the
