@@ -145,6 +145,23 @@ int samnerf_composite_weights(const float* real_bins, const float* sigmas, uint3
  * computes it on the CPU (the sample positions of renderer.py:97, :265). */
 void samnerf_linspace_host(float start, float end, uint32_t steps, float* out_host);
 
+/* The seeded perturbed positions (samnerf_model.perturb_device's contract, stated
+ * there), host only, no GPU needed: the positions of `stage` (0, 1, 2) of ray
+ * `ray` for (seed, offset) -> out_host[num_steps[stage] + 1].  Returns
+ * SAMNERF_EINVAL for a null pointer, stage > 2 or a num_steps entry outside
+ * 1..65535. */
+int samnerf_perturb_host(uint64_t seed, uint64_t offset, const uint32_t* num_steps, uint32_t stage,
+                         uint32_t ray, float* out_host);
+
+/* The same positions on the device, for N rays: bins0 [N][num_steps[0] + 1], u1
+ * [N][num_steps[1] + 1], u2 [N][num_steps[2] + 1], ray order -- the layout of
+ * samnerf_model.perturb, so a render fed these arrays equals the render with
+ * perturb_device = 1 and the same (seed, offset) bit for bit (to log or replay a
+ * step's draws).  Any of the three pointers may be NULL (not written);
+ * num_steps is a host pointer. */
+int samnerf_perturb_fill(uint64_t seed, uint64_t offset, uint32_t N, const uint32_t* num_steps,
+                         float* bins0, float* u1, float* u2, samnerf_stream_t stream);
+
 /* ------------------------------------------------------------ fused path --
  * One hash grid of the model (GridEncoder, gridencoder/grid.py:102-146). */
 typedef struct {
@@ -217,7 +234,9 @@ typedef struct {
      * perturb[0] = the stage-0 bins clamp(linspace(0, 1, T0+1) + (rand - 0.5) / T0, 0, 1)
      * [N][num_steps[0]+1]; perturb[1], perturb[2] = sample_pdf's u = linspace(0.5/T,
      * 1-0.5/T, T) + (rand - 0.5) / T of stages 1 and 2, [N][T] with T = num_steps[s]+1.
-     * Set per call; all NULL = perturb=False (the default), all three or none. */
+     * Set per call; all NULL = perturb=False (the default), all three or none.
+     * (perturb_device below: the same positions drawn inside the kernels from a
+     * seed instead.) */
     const float* perturb[3];
     /* 1: the render workspace already holds this model's packed MLP weights
      * (the f16x3 grid_mlp fragments and the SAM head's weight stream) from an
@@ -227,13 +246,40 @@ typedef struct {
      * pack.  The caller vouches for it (fused.py: the weights' data pointers
      * and torch version counters); the diagnostic library always packs. */
     int reuse_packed;
+    /* perturb=True with the positions drawn inside the kernels (appended: the
+     * fields above keep their offsets).  perturb_device != 0: every perturbed
+     * position is a pure function of (perturb_seed, perturb_offset, stage, ray,
+     * index) -- no position array is allocated, written or read, and the render
+     * does not depend on view_width.  Statistically the reference's sampling
+     * (uniform jitter of one bin width), NOT torch's generator stream: perturb[]
+     * above keeps that contract.  The contract of this mode, exact to the bit:
+     *   generator  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+     *              constants 0x9E3779B9 / 0xBB67AE85, ten rounds)
+     *   key        (seed & 0xffffffff, seed >> 32)
+     *   counter    value i of stage s of ray `ray` (ray order): c0 = (i >> 2) |
+     *              s << 16, c1 = ray, c2 = offset & 0xffffffff, c3 = offset >> 32;
+     *              the value uses output word i & 3
+     *   stages     s = 0: the num_steps[0] + 1 stage-0 bins; s = 1, 2: sample_pdf's
+     *              u of that stage, T = num_steps[s] + 1 values
+     *   uniform    r = (word >> 8) * 2^-24, in [0, 1)
+     *   positions  fp32, one rounding per op, no fma contraction, true division:
+     *              stage 0 clamp(linspace(0, 1, T0 + 1)[i] + (r - 0.5f) / (float)T0,
+     *              0, 1); stages 1, 2 linspace(0.5 / T, 1 - 0.5 / T, T)[j] + (r -
+     *              0.5f) / (float)T, the linspaces as samnerf_linspace_host
+     * (renderer.py:266-271 and :97-101 with r for torch.rand_like).  A call
+     * should use a fresh perturb_offset (a step or chunk counter) per seed.
+     * perturb_device != 0 with any perturb[i] set is SAMNERF_EINVAL.
+     * samnerf_rgb_train_backward must see the forward's seed and offset. */
+    int perturb_device;
+    uint64_t perturb_seed;
+    uint64_t perturb_offset;
 } samnerf_model;
 
 /* Bytes of device workspace samnerf_render_forward needs for N rays. */
 size_t samnerf_render_workspace_size(const samnerf_model* model, uint32_t N);
 
 /* The whole ray-march inner loop for N rays (NeRFRenderer.run in eval mode:
- * perturb = False unless model->perturb is set, background 'last_sample', sum_after_mlp = False,
+ * perturb = False unless model->perturb or model->perturb_device is set, background 'last_sample', sum_after_mlp = False,
  * sam_use_view_direction = True): near/far, 3 proposal rounds with
  * inverse-CDF resampling, hash-grid + SH encoding, sigma / colour MLPs,
  * compositing, view MLP, and (with_sam) the s_grid feature composite plus the
@@ -405,7 +451,7 @@ int samnerf_head_train_backward(const samnerf_model* model, const float* rows,
 
 /* One RGB training step (Trainer.train_step's RGB branch, nerf/utils.py:897-937,
  * over NeRFRenderer.run in train mode, nerf/renderer.py:221-362): the render of
- * N rays (perturbed when model->perturb is set, as the reference trains), the loss
+ * N rays (perturbed when model->perturb or perturb_device is set, as the reference trains), the loss
  * MSE(image, gt) + lambda_proposal * proposal_loss (renderer.py:30-57, when
  * update_proposal) + lambda_distort * distort_loss (renderer.py:17-27, the
  * eff_distloss form) + lambda_entropy * entropy(weights_sum) (utils.py:926-929),
@@ -443,7 +489,8 @@ size_t samnerf_rgb_train_workspace_size(const samnerf_model* model, uint32_t N);
  *   forward: weights [N,32] (or NULL) = the final samples' weights, results['weights']
  *     of renderer.py:350; losses [2] (device) = (proposal_loss,
  *     distort_loss), unweighted; keeps
- *     what the backward reads in `workspace` (same model, rays, N, perturb arrays);
+ *     what the backward reads in `workspace` (same model, rays, N, perturb arrays
+ *     or perturb seed and offset);
  *   backward: grad_image [N,3], grad_weights_sum [N] / grad_depth [N] / grad_weights
  *     [N,32] (NULL = 0), grad_losses [2] (device; NULL = 0, required with
  *     with_proposal) -> the

@@ -26,6 +26,15 @@ int check_launch(const char* what) {
     return SAMNERF_OK;
 }
 
+int check_perturb(const samnerf_model* m, const char* what, bool all_or_none) {
+    if (all_or_none && (!m->perturb[0] != !m->perturb[1] || !m->perturb[0] != !m->perturb[2]))
+        return fail(SAMNERF_EINVAL, "%s: perturb needs all three position arrays or none", what);
+    if (m->perturb_device && (m->perturb[0] || m->perturb[1] || m->perturb[2]))
+        return fail(SAMNERF_EINVAL, "%s: perturb_device draws the positions in the kernels; it cannot be "
+                    "combined with perturb position arrays", what);
+    return SAMNERF_OK;
+}
+
 ResTable make_res_table(uint32_t L, float S, uint32_t H) {
     ResTable t;
     for (uint32_t l = 0; l < 32; ++l) {

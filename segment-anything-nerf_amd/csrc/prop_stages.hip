@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "philox.h"
 #include "raymarch_device.h"
 #include "render_args.h"
 #include "samnerf_common.h"
@@ -88,15 +89,35 @@ struct PropArgs {
     int32_t* inds_out;     // [TN][N] searchsorted indices, or null (parity taps only)
     float* w_out;          // [T][N] composited weights, or null (parity taps only)
     uint32_t pdf_seq;      // diagnostic build, SAMNERF_PDF_SEQ=1: every ray on the sequential phase A
+    // perturb=True drawn in the kernels (samnerf_model.perturb_device, philox.h):
+    // read by the seeded kernel forms only (PHX), which take neither array above
+    PerturbKey phx;
 };
 
 // Bin i of a stage's input for slot r (ray `ray`): stage 0 linspace(0, 1, T+1)
 // or its perturbed copy (renderer.py:264-271), later stages the previous
-// stage's resampled bins (slot-major workspace).
-template <int T, bool FIRST>
+// stage's resampled bins (slot-major workspace).  PHX: the seeded form, stage
+// 0's perturbed bin i of the ray from one generator call.
+template <int T, bool FIRST, bool PHX = false>
 __device__ __forceinline__ float stage_bin(const PropArgs& a, int i, uint32_t r, uint32_t ray) {
-    if constexpr (FIRST) return a.pbins0 ? a.pbins0[(size_t)ray * (T + 1) + i] : a.bins0(i);
+    if constexpr (FIRST && PHX) return perturb_bin0(a.bins0(i), perturb_word(a.phx, 0u, ray, (uint32_t)i), T);
+    else if constexpr (FIRST) return a.pbins0 ? a.pbins0[(size_t)ray * (T + 1) + i] : a.bins0(i);
     else return a.bins_in[(size_t)i * a.N + r];
+}
+
+// A ray's values of one stage read in (mostly) ascending order: the quad last
+// drawn is kept, so a walk over the values costs one generator call per four.
+struct QuadCache {
+    uint32_t q = 0xFFFFFFFFu;
+    Philox4 v;
+};
+__device__ __forceinline__ uint32_t cached_word(QuadCache& c, const PerturbKey& key, uint32_t stage,
+                                                uint32_t ray, uint32_t i) {
+    if ((i >> 2) != c.q) {
+        c.q = i >> 2;
+        c.v = perturb_quad(key, stage, ray, c.q);
+    }
+    return philox_word(c.v, i & 3u);
 }
 
 // Proposal stage, part 1: one thread per (ray, sample).  A wave is 64
@@ -138,13 +159,17 @@ __device__ __forceinline__ void prop_lookup_lay(const PropArgs& a, float x, floa
 #ifndef SAMNERF_PROP_WAVES
 #define SAMNERF_PROP_WAVES 0
 #endif
-template <int T, bool FIRST, int LOOK, uint32_t KD = 0, uint32_t KH = 0>
+// PHX: the seeded form (samnerf_model.perturb_device), stage 0's bins drawn
+// here.  A compile-time switch, last and defaulted: the instantiations of
+// perturb=False and of the array form keep their device code.
+template <int T, bool FIRST, int LOOK, uint32_t KD = 0, uint32_t KH = 0, bool PHX = false>
 __global__ void __launch_bounds__(256)
 #if SAMNERF_PROP_WAVES
 __attribute__((amdgpu_waves_per_eu(SAMNERF_PROP_WAVES, SAMNERF_PROP_WAVES)))
 #endif
 k_prop_sigma(PropArgs a) {
     static_assert(T % 4 == 0, "T must be a multiple of 4");
+    static_assert(FIRST || !PHX, "only stage 0's bins are drawn");
     constexpr uint32_t Q = T / 4;
     const uint32_t b = blockIdx.x, i = b >> 3;
     const uint32_t q = i % Q, g = (b & 7u) * xcd_per((a.N + 63u) / 64u) + i / Q;
@@ -176,9 +201,23 @@ k_prop_sigma(PropArgs a) {
         }
         sn = a.snf[r], sf = a.snf[N + r];                   // k_snf (stage 0) / stage 0 (stage 1)
     }
-    // the ray id: only perturb's per-ray bins need it (FIRST)
-    const uint32_t pray = (FIRST && a.pbins0) ? a.tiles(r) : 0u;
-    const float b0 = stage_bin<T, FIRST>(a, (int)k, r, pray), b1 = stage_bin<T, FIRST>(a, (int)k + 1, r, pray);
+    float b0, b1;
+    if constexpr (PHX) {
+        // the wave's sample index is uniform: bins k and k + 1 are words k & 3
+        // and (k & 3) + 1 of one quad of the ray -- one generator call -- except
+        // in the block's last wave, whose bin k + 1 is word 0 of the next quad
+        const uint32_t ku = __builtin_amdgcn_readfirstlane(k), w = ku & 3u, ray = a.tiles(r);
+        const Philox4 qa = perturb_quad(a.phx, 0u, ray, ku >> 2);
+        uint32_t w1;
+        if (w == 3u) w1 = perturb_quad(a.phx, 0u, ray, (ku >> 2) + 1u).v[0];
+        else w1 = philox_word(qa, w + 1u);
+        b0 = perturb_bin0(a.bins0((int)ku), philox_word(qa, w), T);
+        b1 = perturb_bin0(a.bins0((int)ku + 1), w1, T);
+    } else {
+        // the ray id: only perturb's per-ray bins need it (FIRST)
+        const uint32_t pray = (FIRST && a.pbins0) ? a.tiles(r) : 0u;
+        b0 = stage_bin<T, FIRST>(a, (int)k, r, pray), b1 = stage_bin<T, FIRST>(a, (int)k + 1, r, pray);
+    }
     const float rb_prev = real_bin(sn, sf, b0), rb_next = real_bin(sn, sf, b1);
     const float t = (rb_next + rb_prev) / 2.0f;
     float x = o[0] + d[0] * t, y = o[1] + d[1] * t, z = o[2] + d[2] * t;
@@ -273,7 +312,7 @@ __global__ void __launch_bounds__(256) k_snf(PropArgs a) {
 // position by binary search, and merge-walks its quarter -- the same cdf
 // values and the same interpolation as one walk over the whole ray, so the
 // indices and bins are identical, with a quarter of the dependent steps.
-template <int T, int TN, bool FIRST>
+template <int T, int TN, bool FIRST, bool PHX>
 __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, uint32_t r0, uint32_t nr);
 #ifndef SAMNERF_PDF_SPLIT
 #define SAMNERF_PDF_SPLIT 1                  // phase A split over the block's 4 waves (below)
@@ -282,7 +321,9 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
 #define SAMNERF_PDF_SPLIT_MIN 128            // from this many samples per ray
 #endif
 
-template <int T, int TN, bool FIRST>
+// PHX: the seeded form (as k_prop_sigma's): sample_pdf's u, and stage 0's bins
+// where FIRST, drawn here.
+template <int T, int TN, bool FIRST, bool PHX = false>
 __global__ void __launch_bounds__(256)
 // T = 128: 4 waves per SIMD, the 4 blocks per CU the ds rows' LDS allows
 // (the split phase A otherwise takes 146 VGPRs, 3 waves)
@@ -311,7 +352,7 @@ k_prop_pdf(PropArgs a) {
         for (int k = 0; k < TQ; ++k) row[part * TQ + k] = v[k];
     }
     __syncthreads();
-    prop_pdf_phases<T, TN, FIRST>(a, sw, r0, nr);
+    prop_pdf_phases<T, TN, FIRST, PHX>(a, sw, r0, nr);
 }
 
 // Exact-sum window of a run of float terms (phase A's double cumulative
@@ -360,7 +401,7 @@ __device__ __forceinline__ bool sum_window_exact(const uint32_t* w4) {
 // as before.  The pdf terms (w + 0.01) / sum with w in [0, 1] always pass.
 // One serial chain of 128 steps per ray, one wave per SIMD at the LDS-bound
 // occupancy, was the latency that bounded k_prop_pdf.
-template <int T, int TN, bool FIRST>
+template <int T, int TN, bool FIRST, bool PHX>
 __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, uint32_t r0, uint32_t nr) {
     constexpr int SW = T + 1;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, part = tid >> 6, N = a.N;
@@ -499,8 +540,17 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
     auto bin = [&](int i) -> float { return stage_bin<T, FIRST>(a, i, r, ray); };
     // u_j: linspace, or the perturbed positions (nondecreasing up to rounding:
     // u_j < (j+1)/TN <= u_{j+1} before it, hence the backward step below)
-    const float* pu = a.pu ? a.pu + (size_t)ray * TN : nullptr;
-    auto uj = [&](int j) -> float { return pu ? pu[j] : a.u(j); };
+    const float* pu = (!PHX && a.pu) ? a.pu + (size_t)ray * TN : nullptr;
+    const bool perturbed = PHX || pu;
+    // seeded: the lane walks u_j and (stage 0) the bins around its cdf position
+    // in order, so each keeps the quad it last drew (QuadCache): a call per four
+    // u_j, and per quad of bins the walk enters (below and above share theirs
+    // three times in four)
+    QuadCache cu, cb, ca;
+    auto uj = [&](int j) -> float {
+        if constexpr (PHX) return perturb_u(a.u(j), cached_word(cu, a.phx, FIRST ? 1u : 2u, ray, (uint32_t)j), TN);
+        else return pu ? pu[j] : a.u(j);
+    };
     constexpr int QN = TN / 4;
     const int j0 = (int)part * QN, j1 = part == 3 ? TN : j0 + QN;
     // first index with cdf > u_j0 (cdf is nondecreasing, cdf[0] = 0 <= u)
@@ -514,12 +564,21 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
     int i = lo;
     for (int j = j0; j < j1; ++j) {
         const float u = uj(j);
-        if (pu)
+        if (perturbed)
             while (i > 1 && row[i - 1] > u) --i;
         while (i <= T && row[i] <= u) ++i;
         const int below = i - 1, above = i <= T ? i : T;
         const float g0 = row[below], g1 = row[above];
-        const float b0 = bin(below), b1 = bin(above);
+        float b0, b1;
+        if constexpr (FIRST && PHX) {
+            const uint32_t wb = cached_word(cb, a.phx, 0u, ray, (uint32_t)below);
+            const uint32_t wa = ((uint32_t)above >> 2) == cb.q ? philox_word(cb.v, (uint32_t)above & 3u)
+                                                               : cached_word(ca, a.phx, 0u, ray, (uint32_t)above);
+            b0 = perturb_bin0(a.bins0(below), wb, T);
+            b1 = perturb_bin0(a.bins0(above), wa, T);
+        } else {
+            b0 = bin(below), b1 = bin(above);
+        }
         float t = nan_to_num((u - g0) / (g1 - g0));
         t = fminf(fmaxf(t, 0.0f), 1.0f);
         a.bins_out[(size_t)j * N + r] = b0 + t * (b1 - b0);
@@ -537,7 +596,9 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
 // block leave 4 waves per SIMD instead of k_prop_sigma's 8 to hide the gather
 // latency, and the serial pdf phase holds the block's slots while 3 of its 4
 // waves wait at the barrier.  A selectable variant (SAMNERF_PROP_FUSED=1).
-template <int T, int TN, bool FIRST>
+// PHX: its seeded form (a diagnostic variant like the kernel itself: two
+// generator calls per sample, not amortised).
+template <int T, int TN, bool FIRST, bool PHX = false>
 __global__ void __launch_bounds__(256) k_prop_fused(PropArgs a) {
     constexpr int SW = T + 1;
     __shared__ float sw[64 * SW];
@@ -558,7 +619,7 @@ __global__ void __launch_bounds__(256) k_prop_fused(PropArgs a) {
 #pragma unroll 2
         for (int kk = 0; kk < T / 4; ++kk) {
             const int k = (int)part + 4 * kk;
-            const float b0 = stage_bin<T, FIRST>(a, k, r, ray), b1 = stage_bin<T, FIRST>(a, k + 1, r, ray);
+            const float b0 = stage_bin<T, FIRST, PHX>(a, k, r, ray), b1 = stage_bin<T, FIRST, PHX>(a, k + 1, r, ray);
             const float rb_prev = real_bin(sn, sf, b0), rb_next = real_bin(sn, sf, b1);
             const float t = (rb_next + rb_prev) / 2.0f;
             float x = o[0] + d[0] * t, y = o[1] + d[1] * t, z = o[2] + d[2] * t;
@@ -572,7 +633,7 @@ __global__ void __launch_bounds__(256) k_prop_fused(PropArgs a) {
         }
     }
     __syncthreads();
-    prop_pdf_phases<T, TN, FIRST>(a, sw, r0, nr);
+    prop_pdf_phases<T, TN, FIRST, PHX>(a, sw, r0, nr);
 }
 
 // k_prop_sigma's lookup with compile-time level classes (KD / KH): the 5
@@ -741,7 +802,7 @@ __device__ __forceinline__ void prop_lookup_lay(const PropArgs& a, float x, floa
 // vs 575 VALU cycles per wave) so the box form is slower, 0.88 vs 0.83 ms.
 // Returns the compiled level classes launched (KD | KH << 8), 0 for a run-time
 // form (samnerf_last_forms).
-template <int T, bool FIRST>
+template <int T, bool FIRST, bool PHX>
 uint32_t launch_prop_sigma(int look, uint32_t N, hipStream_t s, const PropArgs& pa) {
     const uint32_t nb = prop_sigma_blocks<T>(N);
     // the reference's proposal grids with a power-of-two grid scale: the
@@ -760,29 +821,30 @@ uint32_t launch_prop_sigma(int look, uint32_t N, hipStream_t s, const PropArgs& 
     const bool lay = (look == kLookPacked || look == kLookAuto) && pa.gs.inv_b2 != 0.0f &&
                      !(pl && atoi(pl) == 0) && small_res && pa.rec;
     if (lay && kd == 0x07u && kh == 0x18u) {
-        k_prop_sigma<T, FIRST, kLookPacked, 0x07u, 0x18u><<<nb, 256, 0, s>>>(pa);
+        k_prop_sigma<T, FIRST, kLookPacked, 0x07u, 0x18u, PHX><<<nb, 256, 0, s>>>(pa);
         return kd | kh << 8;
     }
     if (lay && kd == 0x03u && kh == 0x1Cu) {
-        k_prop_sigma<T, FIRST, kLookPacked, 0x03u, 0x1Cu><<<nb, 256, 0, s>>>(pa);
+        k_prop_sigma<T, FIRST, kLookPacked, 0x03u, 0x1Cu, PHX><<<nb, 256, 0, s>>>(pa);
         return kd | kh << 8;
     }
-    if (look == kLookRef) k_prop_sigma<T, FIRST, kLookRef><<<nb, 256, 0, s>>>(pa);
+    if (look == kLookRef) k_prop_sigma<T, FIRST, kLookRef, 0u, 0u, PHX><<<nb, 256, 0, s>>>(pa);
     else if (look == kLookBox4 && box4_ok(pa.grid))
-        k_prop_sigma<T, FIRST, kLookBox4><<<nb, 256, 0, s>>>(pa);
-    else k_prop_sigma<T, FIRST, kLookPacked><<<nb, 256, 0, s>>>(pa);
+        k_prop_sigma<T, FIRST, kLookBox4, 0u, 0u, PHX><<<nb, 256, 0, s>>>(pa);
+    else k_prop_sigma<T, FIRST, kLookPacked, 0u, 0u, PHX><<<nb, 256, 0, s>>>(pa);
     return 0u;
 }
 
 // One proposal stage: ds per sample, then the pdf -- or both in k_prop_fused.
-template <int T, int TN, bool FIRST>
+// PHX: the seeded kernel forms (only stage 0's sigma kernel reads positions).
+template <int T, int TN, bool FIRST, bool PHX>
 void run_stage(const PropArgs& pa, int look, bool fused, hipStream_t s, uint32_t& form) {
     const uint32_t nb = xcd_blocks(div_up(pa.N, 64));
     if (fused) {
-        k_prop_fused<T, TN, FIRST><<<nb, 256, 0, s>>>(pa);
+        k_prop_fused<T, TN, FIRST, PHX><<<nb, 256, 0, s>>>(pa);
     } else {
-        form = launch_prop_sigma<T, FIRST>(look, pa.N, s, pa);
-        k_prop_pdf<T, TN, FIRST><<<nb, 256, 0, s>>>(pa);
+        form = launch_prop_sigma<T, FIRST, FIRST && PHX>(look, pa.N, s, pa);
+        k_prop_pdf<T, TN, FIRST, PHX><<<nb, 256, 0, s>>>(pa);
     }
 }
 
@@ -829,15 +891,20 @@ void run_proposal_stages(const samnerf_model* m, uint32_t N, const ProposalRun& 
     pa.u = make_lin((float)(0.5 / 65), (float)(1.0 - 0.5 / 65), 65);
     pa.pbins0 = m->perturb[0];
     if (r.mark) r.mark(0, s);
+    // perturb_device: the seeded kernel forms (check_perturb: no arrays then)
+    const bool phx = m->perturb_device != 0;
+    pa.phx = make_perturb_key(m->perturb_seed, m->perturb_offset);
     k_snf<<<div_up(N, 256), 256, 0, s>>>(pa);
-    run_stage<128, 65, true>(pa, r.look, fused, s, forms[0]);
+    if (phx) run_stage<128, 65, true, true>(pa, r.look, fused, s, forms[0]);
+    else run_stage<128, 65, true, false>(pa, r.look, fused, s, forms[0]);
 
     // stage 1: 64 samples -> 33 bins
     set_stage(pa, m, 1, r.st[1]);
     pa.u = make_lin((float)(0.5 / 33), (float)(1.0 - 0.5 / 33), 33);
     pa.bins_in = r.st[0].bins_out;
     if (r.mark) r.mark(1, s);
-    run_stage<64, 33, false>(pa, r.look, fused, s, forms[1]);
+    if (phx) run_stage<64, 33, false, true>(pa, r.look, fused, s, forms[1]);
+    else run_stage<64, 33, false, false>(pa, r.look, fused, s, forms[1]);
 }
 
 // The proposal stages of a training render (rgb_train.hip): the same kernels

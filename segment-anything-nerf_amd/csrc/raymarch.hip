@@ -386,8 +386,7 @@ int render_impl(const samnerf_model* m, const float* rays_o, const float* rays_d
     // at all
     if (cam_near_far && n_cnf != 1 && n_cnf != N)
         return fail(SAMNERF_EINVAL, "render: cam_near_far must have 1 or N rows");
-    if (!m->perturb[0] != !m->perturb[1] || !m->perturb[0] != !m->perturb[2])
-        return fail(SAMNERF_EINVAL, "render: perturb needs all three position arrays or none");
+    if (int prc = check_perturb(m, "render")) return prc;
     Workspace w = carve(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "render: workspace needs %zu bytes, got %zu", w.bytes,

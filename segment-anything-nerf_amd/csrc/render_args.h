@@ -12,7 +12,10 @@ using namespace samnerf;
 // Everything a kernel takes by value stays in an anonymous namespace, here as
 // in the stage files, and so do the kernels: their mangled names
 // (_ZN12_GLOBAL__N_1..., argument types included) are what six rounds of
-// profiles/*.csv and tools/valu_cpi.py name.  Each stage file therefore fills
+// profiles/*.csv and tools/valu_cpi.py name (the proposal kernels' since gained
+// one last template argument, the seeded-perturb switch PHX: "Lb0E" before the
+// closing "EE" of the earlier names; tools/valu_cpi.py and tools/prop_budget.py
+// carry the new ones).  Each stage file therefore fills
 // its own argument struct; the host functions that cross files (namespace
 // samnerf, below) take plain pointers and samnerf:: types only.
 namespace {

@@ -49,6 +49,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "philox.h"
 #include "raymarch_device.h"
 #include "samnerf_common.h"
 #include "sh_device.h"
@@ -752,11 +753,15 @@ struct PropBwdArgs {
     float* grad_grid;         // [rows][2]
     float* grad_rep;          // as RtArgs
     uint32_t rep_levels, rep_floats;
+    // stage 0, perturb drawn in the kernels (samnerf_model.perturb_device): the
+    // seeded kernel forms (PHX) recompute the forward's bins from it (philox.h)
+    PerturbKey phx;
 };
 
-template <int T, bool FIRST>
+template <int T, bool FIRST, bool PHX = false>
 __device__ __forceinline__ float stage_bin_t(const PropBwdArgs& a, int i, uint32_t r) {
-    if constexpr (FIRST) return a.pbins0 ? a.pbins0[(size_t)r * (T + 1) + i] : a.bins0(i);
+    if constexpr (FIRST && PHX) return perturb_bin0(a.bins0(i), perturb_word(a.phx, 0u, r, (uint32_t)i), T);
+    else if constexpr (FIRST) return a.pbins0 ? a.pbins0[(size_t)r * (T + 1) + i] : a.bins0(i);
     else return a.bins_in[(size_t)i * a.N + r];
 }
 
@@ -806,7 +811,10 @@ __device__ __forceinline__ V wave_incl_suffix(V v, uint32_t lane) {
 // suffix scan.  The first form (one thread per ray) ran 128 waves for 8K rays
 // on 1,024 SIMDs, a serial chain each: 0.21 ms for both stages, step 3.67 ->
 // 3.57 ms with this one.
-template <int T, bool FIRST>
+// PHX (both kernels below): stage 0 with the bins drawn in the kernels
+// (perturb_device); a defaulted compile-time switch, so the other forms keep
+// their device code.
+template <int T, bool FIRST, bool PHX = false>
 __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
     constexpr int E = T / 64;
     __shared__ float Cw[4][T + 2];
@@ -840,8 +848,8 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
     if (lane < (uint32_t)kT) {
         const uint32_t i = lane;
         const float t0lo = a.bins2[(size_t)i * N + r], t0hi = a.bins2[(size_t)(i + 1) * N + r];
-        int lo = upper_bound_t(T, t0lo, [&](int q) { return stage_bin_t<T, FIRST>(a, q, r); }) - 1;
-        int hi = upper_bound_t(T, t0hi, [&](int q) { return stage_bin_t<T, FIRST>(a, q + 1, r); });
+        int lo = upper_bound_t(T, t0lo, [&](int q) { return stage_bin_t<T, FIRST, PHX>(a, q, r); }) - 1;
+        int hi = upper_bound_t(T, t0hi, [&](int q) { return stage_bin_t<T, FIRST, PHX>(a, q + 1, r); });
         lo = min(max(lo, 0), T - 1);
         hi = min(max(hi, 0), T - 1);
         const float w = cw[hi + 1] - cw[lo];
@@ -900,7 +908,7 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
 // the stage (network.py:248-259) re-evaluated, then its backward.
 constexpr uint32_t kPropW = 176;            // prop_mlp gradients: [16,10] then [1,16]
 
-template <int T, bool FIRST>
+template <int T, bool FIRST, bool PHX = false>
 __global__ void __launch_bounds__(256) k_rt_prop_bwd(PropBwdArgs a) {
     __shared__ float sstage[4][384];
     __shared__ float sred[4][kPropW];
@@ -926,8 +934,8 @@ __global__ void __launch_bounds__(256) k_rt_prop_bwd(PropBwdArgs a) {
         d[c] = a.rays_d[(size_t)r * 3 + c];
     }
     const float sn = a.snf[r], sf = a.snf[N + r];
-    const float rbp = real_bin(sn, sf, stage_bin_t<T, FIRST>(a, (int)k, r));
-    const float rbn = real_bin(sn, sf, stage_bin_t<T, FIRST>(a, (int)k + 1, r));
+    const float rbp = real_bin(sn, sf, stage_bin_t<T, FIRST, PHX>(a, (int)k, r));
+    const float rbn = real_bin(sn, sf, stage_bin_t<T, FIRST, PHX>(a, (int)k + 1, r));
     const float t = (rbn + rbp) / 2.0f;
     float x = o[0] + d[0] * t, y = o[1] + d[1] * t, z = o[2] + d[2] * t;
     contract3(x, y, z);
@@ -1190,6 +1198,7 @@ int rt_setup(const samnerf_model* m, const float* rays_o, const float* rays_d, u
     pb.snf = w.p.snf;
     pb.bins0 = make_linspace(0.0f, 1.0f, 129);
     pb.pbins0 = m->perturb[0];
+    pb.phx = make_perturb_key(m->perturb_seed, m->perturb_offset);
     pb.bins_in = w.p.bins1;
     pb.bins2 = w.p.bins2;
     pb.wf = a.w;
@@ -1224,7 +1233,8 @@ int rt_forward(const samnerf_model* m, const float* rays_o, const float* rays_d,
     k_rt_composite_h<<<div_up(N, 8), 256, 0, s>>>(c.a);
     if (with_prop) {
         rt_prop_stage(m, c, w, 0);
-        k_rt_prop_ray_w<128, true><<<div_up(N, 4), 256, 0, s>>>(c.pb);
+        if (m->perturb_device) k_rt_prop_ray_w<128, true, true><<<div_up(N, 4), 256, 0, s>>>(c.pb);
+        else k_rt_prop_ray_w<128, true><<<div_up(N, 4), 256, 0, s>>>(c.pb);
         rt_prop_stage(m, c, w, 1);
         k_rt_prop_ray_w<64, false><<<div_up(N, 4), 256, 0, s>>>(c.pb);
     }
@@ -1285,6 +1295,7 @@ int rt_backward(const samnerf_model* m, uint32_t N, bool with_prop, const samner
             const uint32_t T = st ? 64u : 128u;
             const uint32_t blocks = div_up((uint64_t)T * N, 256);
             if (st) k_rt_prop_bwd<64, false><<<blocks, 256, 0, s>>>(pb);
+            else if (m->perturb_device) k_rt_prop_bwd<128, true, true><<<blocks, 256, 0, s>>>(pb);
             else k_rt_prop_bwd<128, true><<<blocks, 256, 0, s>>>(pb);
             rep_sum(w.rep_floats[1 + st], g->prop[st]);
             k_rt_outer_sum<<<div_up(160, 16), 256, 0, s>>>(w.slab, kPropW, 0u, 160u, blocks, g->prop_mlp[st][0]);
@@ -1293,8 +1304,6 @@ int rt_backward(const samnerf_model* m, uint32_t N, bool with_prop, const samner
     }
     return SAMNERF_OK;
 }
-
-bool perturb_ok(const samnerf_model* m) { return !m->perturb[0] == !m->perturb[1] && !m->perturb[0] == !m->perturb[2]; }
 
 }  // namespace
 
@@ -1315,8 +1324,7 @@ int samnerf_rgb_train_forward(const samnerf_model* m, const float* rays_o, const
         return fail(SAMNERF_EINVAL, "rgb_train_forward: null pointer");
     if (cam_near_far && n_cnf != 1 && n_cnf != N)
         return fail(SAMNERF_EINVAL, "rgb_train_forward: cam_near_far must have 1 or N rows");
-    if (!perturb_ok(m))
-        return fail(SAMNERF_EINVAL, "rgb_train_forward: perturb needs all three position arrays or none");
+    if (int prc = check_perturb(m, "rgb_train_forward")) return prc;
     RtWorkspace w = carve_rt(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "rgb_train_forward: workspace needs %zu bytes, got %zu", w.bytes,
@@ -1342,6 +1350,7 @@ int samnerf_rgb_train_backward(const samnerf_model* m, const float* rays_o, cons
     if (!rays_o || !rays_d || !grad_image) return fail(SAMNERF_EINVAL, "rgb_train_backward: null pointer");
     if (with_proposal && !grad_losses)
         return fail(SAMNERF_EINVAL, "rgb_train_backward: the proposal backward needs grad_losses");
+    if (int prc = check_perturb(m, "rgb_train_backward", false)) return prc;
     RtWorkspace w = carve_rt(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "rgb_train_backward: workspace needs %zu bytes, got %zu", w.bytes,
@@ -1373,8 +1382,7 @@ int samnerf_rgb_train_step(const samnerf_model* m, const float* rays_o, const fl
         return fail(SAMNERF_EINVAL, "rgb_train_step: null pointer");
     if (cam_near_far && n_cnf != 1 && n_cnf != N)
         return fail(SAMNERF_EINVAL, "rgb_train_step: cam_near_far must have 1 or N rows");
-    if (!perturb_ok(m))
-        return fail(SAMNERF_EINVAL, "rgb_train_step: perturb needs all three position arrays or none");
+    if (int prc = check_perturb(m, "rgb_train_step")) return prc;
     RtWorkspace w = carve_rt(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "rgb_train_step: workspace needs %zu bytes, got %zu", w.bytes,

@@ -32,6 +32,10 @@ inline const char* diag_env(const char* name) {
 }
 int check_launch(const char* what);
 
+// samnerf_model's perturb sources: the position arrays all three or none
+// (all_or_none), and never together with perturb_device (philox.h)
+int check_perturb(const samnerf_model* m, const char* what, bool all_or_none = true);
+
 inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Hash primes of the coherent spatial hash (gridencoder.cu:49).

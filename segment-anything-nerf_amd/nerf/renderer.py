@@ -8,7 +8,10 @@ unfused op sequence on the GPU with the drop-in encoders -- the
 "reference-equivalent" single-GPU baseline of BASELINE.md and the path for
 options the fused kernels do not cover (training-mode bookkeeping and
 autograd).  Perturbed sampling runs fused: the perturbed positions are drawn
-with torch's generator in the reference's order (fused.perturbed_positions).
+with torch's generator in the reference's order (fused.perturbed_positions),
+or -- perturb_rng = "philox", opt-in -- inside the kernels from a seed and a
+per-call counter (fused.PhiloxPerturb: statistically the same sampling, not
+torch's stream; no position arrays).
 Staged rendering chunks rays like renderer.py:185-219 but,
 unlike the reference, also works with return_feats (flat [N,256] rows are
 reshaped once at the end, fixing the SURVEY.md 0.3 crash).
@@ -133,6 +136,14 @@ class NeRFRenderer(nn.Module):
         # reference's semantics); read by samnerf_amd.fused.FusedRenderer
         self.head_mode = 0
         self.t_thresh = 0.0
+        # perturb=True on the fused paths: "torch" (default) draws the positions
+        # with torch's generator as the reference does; "philox" has the kernels
+        # draw them from PhiloxPerturb(perturb_seed, k), k counting this
+        # renderer's dispatched fused calls (staged chunks and successive training
+        # steps draw differently).  run_torch always draws with torch.
+        self.perturb_rng = "torch"
+        self.perturb_seed = 0
+        self._perturb_calls = 0
 
     def forward(self, x, d, **kwargs):
         raise NotImplementedError()
@@ -223,6 +234,20 @@ class NeRFRenderer(nn.Module):
                 and (not o.with_sam or o.sam_use_view_direction)
                 and (not torch.is_tensor(bg_color) or bg_color.numel() == 1))
 
+    def _fused_perturb(self, perturb):
+        """What a dispatched fused call gets as perturb=: the caller's value, or
+        under perturb_rng = "philox" the seeded source of this call for a plain
+        perturb=True.  Every dispatched call advances the counter."""
+        if self.perturb_rng not in ("torch", "philox"):
+            raise ValueError(f"perturb_rng {self.perturb_rng!r}: 'torch' or 'philox'")
+        k = self._perturb_calls
+        self._perturb_calls = k + 1
+        if self.perturb_rng == "philox" and perturb and not isinstance(perturb, (tuple, list)):
+            from samnerf_amd.fused import PhiloxPerturb
+            if not isinstance(perturb, PhiloxPerturb):
+                return PhiloxPerturb(int(self.perturb_seed), k)
+        return perturb
+
     def run(self, rays_o, rays_d, bg_color=None, perturb=False, cam_near_far=None,
             update_proposal=True, return_feats=0, return_mask=0, H=None, W=None, **kwargs):
         if self._fused_mask_train_ok(rays_o, bg_color, perturb, return_feats, return_mask):
@@ -234,8 +259,8 @@ class NeRFRenderer(nn.Module):
             from samnerf_amd.fused import FusedRenderer, render_rgb_train
             if self._fused is None or self._fused.net is not self:
                 self._fused = FusedRenderer(self)
-            return render_rgb_train(self._fused, rays_o, rays_d, cam_near_far, bg_color, perturb,
-                                    update_proposal)
+            return render_rgb_train(self._fused, rays_o, rays_d, cam_near_far, bg_color,
+                                    self._fused_perturb(perturb), update_proposal)
         if self._fused_ok(rays_o, perturb, return_mask, kwargs):
             from samnerf_amd.fused import FusedRenderer
             if self._fused is None or self._fused.net is not self:
@@ -244,7 +269,7 @@ class NeRFRenderer(nn.Module):
             vw = W if (W is not None and n % W == 0) else 0      # a whole number of image rows
             out = self._fused.render(rays_o, rays_d, cam_near_far, bg_color,
                                      feats=return_feats > 0, view_width=vw, mask=return_mask > 0,
-                                     perturb=perturb)
+                                     perturb=self._fused_perturb(perturb))
             samvit = out.pop("samvit", None)
             if return_feats > 0 and samvit is not None:
                 out["samvit"] = samvit.view(H, W, -1) if H is not None else samvit

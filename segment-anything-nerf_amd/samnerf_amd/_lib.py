@@ -18,6 +18,7 @@ _f64 = ctypes.c_double
 _int = ctypes.c_int
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
+_u64 = ctypes.c_uint64
 
 
 class SamnerfUnavailable(RuntimeError):
@@ -39,7 +40,8 @@ class SamnerfModel(ctypes.Structure):
                 ("t_thresh", _f32), ("view_width", _u32),
                 ("with_mask", _int), ("mask_kind", _int), ("m_grid", SamnerfGrid), ("mask_w", _vp * 8),
                 ("mask_out", _u32),
-                ("sum_after_mlp", _int), ("perturb", _vp * 3), ("reuse_packed", _int)]
+                ("sum_after_mlp", _int), ("perturb", _vp * 3), ("reuse_packed", _int),
+                ("perturb_device", _int), ("perturb_seed", _u64), ("perturb_offset", _u64)]
 
 
 _SIGS = {
@@ -64,6 +66,8 @@ _SIGS = {
     "samnerf_sample_pdf": ([_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp], _int),
     "samnerf_composite_weights": ([_vp, _vp, _u32, _u32, _vp, _vp], _int),
     "samnerf_linspace_host": ([_f32, _f32, _u32, ctypes.POINTER(_f32)], None),
+    "samnerf_perturb_host": ([_u64, _u64, ctypes.POINTER(_u32), _u32, _u32, ctypes.POINTER(_f32)], _int),
+    "samnerf_perturb_fill": ([_u64, _u64, _u32, ctypes.POINTER(_u32), _vp, _vp, _vp, _vp], _int),
     "samnerf_render_workspace_size": ([ctypes.POINTER(SamnerfModel), _u32], _sz),
     "samnerf_render_forward": ([ctypes.POINTER(SamnerfModel), _vp, _vp, _u32, _vp, _u32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _int),

@@ -8,6 +8,7 @@ place (torch layout); nothing is copied or cached between calls except the
 workspace buffer.
 """
 import ctypes
+import dataclasses
 
 import numpy as np
 import torch
@@ -59,6 +60,66 @@ def perturbed_positions(N, num_steps, device):
         u = u + (torch.rand_like(u) - 0.5) / T
         out.append(u.contiguous())
     return tuple(out)
+
+
+@dataclasses.dataclass(frozen=True)
+class PhiloxPerturb:
+    """perturb=True with the positions drawn inside the kernels
+    (samnerf_model.perturb_device): every perturbed position is a pure function
+    of (seed, offset, stage, ray, index) under Philox4x32-10 -- the contract is
+    in include/samnerf_hip.h.  Statistically the reference's sampling, not
+    torch's generator stream (perturb=True keeps that).  Pass as `perturb=` to
+    FusedRenderer.render, render_rgb_train and rgb_train_step_fused; use a new
+    offset for every call that should draw differently."""
+    seed: int
+    offset: int = 0
+
+    def __post_init__(self):
+        for name in ("seed", "offset"):
+            v = getattr(self, name)
+            if not (isinstance(v, int) and 0 <= v < 1 << 64):
+                raise ValueError(f"PhiloxPerturb: {name} must be an integer in [0, 2^64)")
+
+
+def set_perturb(m, pert):
+    """Point the samnerf_model struct `m` at one perturb source for a call: None
+    (perturb=False), a PhiloxPerturb, or the (bins0, u1, u2) tensors; the caller
+    keeps the tensors alive and calls set_perturb(m, None) afterwards."""
+    seeded = isinstance(pert, PhiloxPerturb)
+    m.perturb_device = int(seeded)
+    m.perturb_seed = pert.seed if seeded else 0
+    m.perturb_offset = pert.offset if seeded else 0
+    for i in range(3):
+        m.perturb[i] = None if (pert is None or seeded) else _param(pert[i], f"perturb[{i}]")
+
+
+def _steps3(num_steps):
+    return (ctypes.c_uint32 * 3)(*[int(v) for v in num_steps])
+
+
+def perturb_host(seed, offset, num_steps, stage, ray):
+    """The seeded positions of one ray's stage (0, 1, 2), computed on the host
+    by the library from the header the kernels use (samnerf_perturb_host; needs
+    no GPU): float32 numpy [num_steps[stage] + 1]."""
+    out = np.empty(int(num_steps[stage]) + 1, np.float32)
+    check(lib().samnerf_perturb_host(int(seed), int(offset), _steps3(num_steps), int(stage), int(ray),
+                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), "perturb_host")
+    return out
+
+
+def perturb_fill(seed, offset, N, num_steps, device, want=(True, True, True)):
+    """The arrays a PhiloxPerturb(seed, offset) render of N rays draws,
+    materialised on the device (samnerf_perturb_fill): (bins0 [N, T0+1], u1
+    [N, T1+1], u2 [N, T2+1]), the layout of render(perturb=<tuple>), which then
+    gives the seeded render bit for bit -- to log or replay a step's draws.
+    want[i] = False leaves array i out (None in the tuple)."""
+    dev = torch.device(device)
+    out = tuple(torch.empty(N, int(num_steps[i]) + 1, device=dev) if want[i] else None for i in range(3))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        check(lib().samnerf_perturb_fill(int(seed), int(offset), int(N), _steps3(num_steps), _ptr(out[0]),
+                                         _ptr(out[1]), _ptr(out[2]), stream), "perturb_fill")
+    return out
 
 
 def ray_of_slots(N, view_width):
@@ -283,8 +344,9 @@ class FusedRenderer:
         -- and returned as views of it.
         perturb: False (default), True (draw the perturbed sample positions
         with torch's generator, perturbed_positions -- the reference's
-        perturb=True), or a (bins0, u1, u2) tuple of them [N, 129], [N, 65],
-        [N, 33] (samnerf_model.perturb)."""
+        perturb=True), a (bins0, u1, u2) tuple of them [N, 129], [N, 65],
+        [N, 33] (samnerf_model.perturb), or a PhiloxPerturb(seed, offset): the
+        kernels draw the positions themselves (no arrays)."""
         rays_o = rays_o.contiguous().float()
         rays_d = rays_d.contiguous().float()
         N = rays_o.shape[0]
@@ -296,18 +358,16 @@ class FusedRenderer:
         # 2: a training render (mask_logits=False): the adaptive heads keep their per-ray input sums
         m.with_mask = (2 if not mask_logits else 1) if mask else 0
         pert = None
-        if isinstance(perturb, (tuple, list)) or perturb:      # the GUI passes spp (an int) as perturb
+        if isinstance(perturb, PhiloxPerturb):
+            pert = perturb
+        elif isinstance(perturb, (tuple, list)) or perturb:    # the GUI passes spp (an int) as perturb
             pert = tuple(perturb) if isinstance(perturb, (tuple, list)) else \
                 perturbed_positions(N, list(m.num_steps), dev)
             shapes = [(N, int(m.num_steps[0]) + 1), (N, int(m.num_steps[1]) + 1), (N, int(m.num_steps[2]) + 1)]
             if len(pert) != 3 or any(tuple(t.shape) != sh for t, sh in zip(pert, shapes)):
                 raise ValueError(f"fused render: perturb arrays must have shapes {shapes}")
             pert = tuple(t.contiguous().float() for t in pert)
-            for i in range(3):
-                m.perturb[i] = _param(pert[i], f"perturb[{i}]")
-        else:
-            for i in range(3):
-                m.perturb[i] = None
+        set_perturb(m, pert)
         pack_key = None
         if own_workspace:
             need = lib().samnerf_render_workspace_size(ctypes.byref(m), N)
@@ -396,8 +456,7 @@ class FusedRenderer:
         finally:
             if taps:
                 lib().samnerf_set_taps(None, 0)
-            for i in range(3):
-                m.perturb[i] = None
+            set_perturb(m, None)
             m.reuse_packed = 0
         out = {"image": image, "depth": depth, "weights_sum": wsum}
         if mask and mask_logits:
@@ -666,16 +725,14 @@ class _FusedRGBTrain(torch.autograd.Function):
         losses = torch.zeros(2, device=dev)
         n_cnf = 0 if cnf is None else cnf.shape[0]
         try:
-            for i in range(3):
-                m.perturb[i] = None if pert is None else _param(pert[i], f"perturb[{i}]")
+            set_perturb(m, pert)
             check(lib().samnerf_rgb_train_forward(
                 ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, float(bg), int(with_prop),
                 _ptr(image), _ptr(depth), _ptr(wsum), _ptr(weights), _ptr(losses), _ptr(ws), need,
                 _stream(rays_o)),
                 "rgb_train_forward")
         finally:
-            for i in range(3):
-                m.perturb[i] = None
+            set_perturb(m, None)
         ctx.state = (renderer, m, rays_o, rays_d, bg, pert, with_prop, ws, need, list(renderer._keep))
         ctx.shapes = [p.shape for p in params]
         # outputs the loss does not use arrive as None (no zero tensors to
@@ -713,15 +770,13 @@ class _FusedRGBTrain(torch.autograd.Function):
                 for i in range(2):
                     g.prop_mlp[q][i] = grads[9 + 2 * q + i].data_ptr()
         try:
-            for i in range(3):
-                m.perturb[i] = None if pert is None else _param(pert[i], f"perturb[{i}]")
+            set_perturb(m, pert)             # the forward's arrays, or its (seed, offset)
             check(lib().samnerf_rgb_train_backward(
                 ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, float(bg), int(with_prop), _ptr(g_img),
                 _ptr(g_ws), _ptr(g_dp), _ptr(g_w), _ptr(g_loss),
                 ctypes.byref(g), _ptr(ws), need, _stream(g_img)), "rgb_train_backward")
         finally:
-            for i in range(3):
-                m.perturb[i] = None
+            set_perturb(m, None)
         if not with_prop:
             grads = grads[:7] + [None] * (len(grads) - 7)
         return (None,) * 7 + tuple(grads)
@@ -733,7 +788,8 @@ def render_rgb_train(renderer, rays_o, rays_d, cam_near_far=None, bg_color=None,
     grad (renderer.py:221-362): image, depth, weights_sum, num_points and --
     when lambda_proposal > 0 and update_proposal -- proposal_loss, when
     lambda_distort > 0 distort_loss, all differentiable on the HIP training
-    kernels (rgb_train.hip)."""
+    kernels (rgb_train.hip).  perturb as FusedRenderer.render's (False, True,
+    the three arrays, or a PhiloxPerturb)."""
     net = renderer.net
     opt = net.opt
     rays_o = rays_o.contiguous().float()
@@ -743,7 +799,9 @@ def render_rgb_train(renderer, rays_o, rays_d, cam_near_far=None, bg_color=None,
                                         float(bg_color.reshape(())))
     m = renderer.model()
     pert = None
-    if isinstance(perturb, (tuple, list)) or perturb:
+    if isinstance(perturb, PhiloxPerturb):
+        pert = perturb                   # drawn in the kernels, forward and backward alike
+    elif isinstance(perturb, (tuple, list)) or perturb:
         pert = tuple(perturb) if isinstance(perturb, (tuple, list)) else \
             perturbed_positions(N, list(m.num_steps), rays_o.device)
         pert = tuple(t.contiguous().float() for t in pert)

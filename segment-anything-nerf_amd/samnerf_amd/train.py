@@ -52,7 +52,8 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
                          cam_near_far=None, perturb=True):
     """rgb_train_step on the HIP training kernels (samnerf_rgb_train_step,
     csrc/rgb_train.hip): one C call renders the rays (the reference's perturbed
-    sampling, drawn with torch's generator in its order), forms the loss of
+    sampling, drawn with torch's generator in its order, or inside the kernels
+    for perturb=PhiloxPerturb(seed, offset)), forms the loss of
     utils.py:917-931 and writes every trained tensor's gradient into .grad --
     what loss.backward() leaves there (the proposal tensors' .grad is None on
     the steps the reference does not update them, utils.py:912-913).  Returns
@@ -64,7 +65,7 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     import ctypes
 
     from ._lib import SamnerfRgbGrads, SamnerfRgbTrainOpts, check, lib
-    from .fused import FusedRenderer, perturbed_positions, rgb_train_params
+    from .fused import FusedRenderer, PhiloxPerturb, perturbed_positions, rgb_train_params, set_perturb
     from .ops import _ptr, _stream
 
     opt = model.opt
@@ -89,12 +90,13 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     m.view_width = 0
     m.with_mask = 0
     pert = None
-    if isinstance(perturb, (tuple, list)) or perturb:
+    if isinstance(perturb, PhiloxPerturb):
+        pert = perturb                   # the kernels draw the positions (no arrays)
+    elif isinstance(perturb, (tuple, list)) or perturb:
         pert = tuple(perturb) if isinstance(perturb, (tuple, list)) else \
             perturbed_positions(N, list(m.num_steps), dev)
         pert = tuple(t.contiguous().float() for t in pert)
-    for i in range(3):
-        m.perturb[i] = ctypes.c_void_p(pert[i].data_ptr()) if pert is not None else None
+    set_perturb(m, pert)
     o = SamnerfRgbTrainOpts()
     o.lambda_proposal = float(getattr(opt, "lambda_proposal", 0.0))
     o.lambda_distort = float(getattr(opt, "lambda_distort", 0.0))
@@ -142,8 +144,7 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
             ctypes.byref(o), _ptr(image), _ptr(depth), _ptr(wsum), _ptr(loss), ctypes.byref(g),
             _ptr(ws), need, _stream(rays_o)), "rgb_train_step")
     finally:
-        for i in range(3):
-            m.perturb[i] = None
+        set_perturb(m, None)
     for p, t in zip(trained, scratch):
         if p.grad is None:
             p.grad = t

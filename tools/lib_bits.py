@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fingerprints of the outputs of one library build (SAMNERF_LIB, or the
 in-tree product): the headline view on the default and the parity-weight
-scene, the sphere scene, the --with_mask view and one mask-training forward,
+scene, the sphere scene, an array-perturbed view, the --with_mask view and one mask-training forward,
 as sha256 prefixes of the raw bytes.  Two builds whose lines match are
 bit-identical on these workloads (A/B of kernel forms that must keep the
 bits).  usage (GPU box): [SAMNERF_LIB=...] python tools/lib_bits.py"""
@@ -38,6 +38,13 @@ def main():
             net, _, _ = bench.build_net(True, dev, **kw)
             o = FusedRenderer(net, head_mode=head_mode).render(ro, rd, view_width=W)
             out[f"{tag}_h{head_mode}"] = {k: sha(o[k]) for k in ("image", "depth", "samvit")}
+    # the array-perturbed render (samnerf_model.perturb): torch's draws from a fixed seed
+    from samnerf_amd.fused import perturbed_positions
+    net, _, _ = bench.build_net(True, dev, emb_scale=0.5)
+    torch.manual_seed(7)
+    draws = perturbed_positions(H * W, [128, 64, 32], dev)
+    o = FusedRenderer(net).render(ro, rd, view_width=W, perturb=draws)
+    out["parity_perturbed_h0"] = {k: sha(o[k]) for k in ("image", "depth", "samvit")}
     r = bench.mask_view(dev, 1, 1, 0, ref_rays=16384)
     out["mask_logits"] = r["logits_sha16"]
     _, loss = bench.mask_train_steps(dev, 1, 0)          # the first step's forward loss (before any update)

@@ -32,8 +32,8 @@ sys.path.insert(0, __file__.rsplit("/", 1)[0])
 from valu_budget import cycles, kernel_lines  # noqa: E402
 
 KERNELS = {
-    "k_prop_sigma<128, DDDHH>": "_ZN12_GLOBAL__N_112k_prop_sigmaILi128ELb1ELi0ELj7ELj24EEEvNS_8PropArgsE",
-    "k_prop_sigma<64, DDHHH>": "_ZN12_GLOBAL__N_112k_prop_sigmaILi64ELb0ELi0ELj3ELj28EEEvNS_8PropArgsE",
+    "k_prop_sigma<128, DDDHH>": "_ZN12_GLOBAL__N_112k_prop_sigmaILi128ELb1ELi0ELj7ELj24ELb0EEEvNS_8PropArgsE",
+    "k_prop_sigma<64, DDHHH>": "_ZN12_GLOBAL__N_112k_prop_sigmaILi64ELb0ELi0ELj3ELj28ELb0EEEvNS_8PropArgsE",
 }
 PHASES = ["record", "bins", "locate", "rows", "gather", "trilinear", "mlp", "out"]
 

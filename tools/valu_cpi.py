@@ -25,8 +25,8 @@ SRC = os.path.join(ROOT, "segment-anything-nerf_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
          "-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-S"]
 STAGES = {
-    "prop0": ("prop_stages.hip", "_ZN12_GLOBAL__N_112k_prop_sigmaILi128ELb1ELi0ELj7ELj24EEEvNS_8PropArgsE"),
-    "prop1": ("prop_stages.hip", "_ZN12_GLOBAL__N_112k_prop_sigmaILi64ELb0ELi0ELj3ELj28EEEvNS_8PropArgsE"),
+    "prop0": ("prop_stages.hip", "_ZN12_GLOBAL__N_112k_prop_sigmaILi128ELb1ELi0ELj7ELj24ELb0EEEvNS_8PropArgsE"),
+    "prop1": ("prop_stages.hip", "_ZN12_GLOBAL__N_112k_prop_sigmaILi64ELb0ELi0ELj3ELj28ELb0EEEvNS_8PropArgsE"),
     "final": ("final_stage.hip", "_ZN12_GLOBAL__N_17k_finalILi32ELi1ELb0ELb0ELb0ELb0ELi0ELi1ELb0EEEvNS_9FinalArgsE"),
     "s_grid": ("sgrid.hip", "_ZN12_GLOBAL__N_112k_sgrid_box4ILi32ELb0EEEvNS_9SgridArgsE"),
     "sam_head": ("sam_head.hip", None),     # the product head: k_sam_head_w8<4, 8, true> (round 6)
