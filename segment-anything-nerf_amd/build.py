@@ -114,9 +114,12 @@ def build(jobs=None, verbose=True, diag=True):
     os.makedirs(DIAG_OBJ_DIR, exist_ok=True)
     jobs = jobs or min(2 * len(SOURCES), os.cpu_count() or 4, 8)
     own = [src for src in SOURCES if diag and _reads_diag_switch(src)]
-    # the diagnostic objects first: sam_head.hip's (its variant forms) takes
-    # about three times as long as any other object, so it bounds the build
-    # and has to start at once
+    # Four objects take 24-29 s on 8 CPUs and no other more than 10: both
+    # builds' final_stage.hip, the product grid_encoder.hip and the diagnostic
+    # sam_head.hip (133 s before its superseded forms were retired, when it
+    # bounded the build alone).  With the diagnostic objects first all four
+    # start within seconds and the build takes about one of them: 30 s
+    # against 36-38 s with the product objects first (133 s before).
     work = [(src, True) for src in own] + [(src, False) for src in SOURCES]
     with cf.ThreadPoolExecutor(jobs) as ex:
         objs = dict(zip(work, ex.map(lambda a: _compile(*a), work)))

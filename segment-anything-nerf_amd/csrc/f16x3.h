@@ -65,27 +65,17 @@ __device__ __forceinline__ float exp2i(int k) {
 }
 
 // hi / lo halves of 8 values times s (s a power of two, so x * s is exact),
-// packed as two f16 per dword: hi = f16(x s), lo = f16(x s - hi), each one
-// v_fma_mix (fp32 fma of f32 / f16 sources rounded once to f16): 4
-// instructions per pair where multiply, convert, convert back, subtract and
-// convert took 6.  The same bits as that sequence (x s and x s - hi are exact
-// in fp32, so both round the same value once).
+// packed as two f16 per dword: hi = f16(x s), lo = f16(x s - hi); x s and
+// x s - hi are exact in fp32, so each half is one rounding to fp16.
 //
-// Wait states (nothing inside an asm string is padded by hipcc): both mix
-// forms write half of their destination and keep the other half (a
-// read-modify-write of the dword), and a VALU that reads a VGPR right after
-// such a partial write needs one wait state (gfx950's dst-sel forwarding
-// hazard).  So every dword's partial writes and reads here are 4 instructions
-// apart: the four hi dwords' low halves, then their high halves, then the lo
-// dwords' low halves (reading the hi dwords), then their high halves; the
-// string ends with s_nop 1 because its outputs feed MFMA A/B operands, which
-// need two wait states after a VALU write (the guide's VALU -> MFMA operand
-// rule; it also covers the last partial write).  The round-1 to round-3 form
-// (hi, then lo, of each pair back to back) read the hi dword one instruction
-// after its partial write: on a busy SIMD another wave's instruction usually
-// sat between them, so the outputs were right on most launches and wrong on a
-// few (the k_final prefetch variants' "nondeterminism"); the
-// first round-4 form still wrote each hi dword's two halves back to back.
+// Nothing inside an asm string is padded by hipcc, so the string keeps its
+// own wait states.  The forms of rounds 1-5 did the split with v_fma_mix,
+// which writes half a dword (a read-modify-write with gfx950's dst-sel
+// forwarding hazard): the round-1 to round-3 string read the hi dword one
+// instruction after its partial write and was wrong on a few launches (the
+// k_final prefetch variants' "nondeterminism"), the round-4
+// string spaced them and was right but slow (profiles/r5sp_split_form_ab.txt).
+// Both are retired; the full-dword form below is the only asm form.
 #if defined(SAMNERF_F16X3_NOASM)
 // The same split in plain C (v_pk_mul_f32, v_cvt_pk_f16_f32, conversions back,
 // a subtraction, v_cvt_pk_f16_f32 again): full-dword writes the compiler
@@ -104,27 +94,8 @@ __device__ __forceinline__ void split8_f16(const float* v, float s, uint4& hi, u
     hi = make_uint4(h[0], h[1], h[2], h[3]);
     lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
-#elif defined(SAMNERF_AB_OLDSPLIT)   // timing A/B only: the round-3 form (hazard-exposed)
-__device__ __forceinline__ void split_pair_f16_old(float x, float y, float s, uint32_t& hi, uint32_t& lo) {
-    uint32_t h, l;
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(h), "=&v"(l)
-        : "v"(x), "v"(y), "v"(s));
-    hi = h;
-    lo = l;
-}
-template <bool LEAD = false>   // timing variants: no leading pad
-__device__ __forceinline__ void split8_f16(const float* v, float s, uint4& hi, uint4& lo) {
-    split_pair_f16_old(v[0], v[1], s, hi.x, lo.x);
-    split_pair_f16_old(v[2], v[3], s, hi.y, lo.y);
-    split_pair_f16_old(v[4], v[5], s, hi.z, lo.z);
-    split_pair_f16_old(v[6], v[7], s, hi.w, lo.w);
-}
-#elif !defined(SAMNERF_SPLIT_MIX)
-// Round 5: the same split on full-dword conversions.  v_fma_mix issues at a
+#else
+// The split on full-dword conversions (round 5).  v_fma_mix issues at a
 // quarter of v_fma_f32's rate on gfx950 (8.2 cycles per wave64 instruction
 // against 2.2; v_cvt_pk_f16_f32 / v_cvt_f32_f16 4.1, v_mul_f32 / v_sub_f32
 // 2.2: tools/valu_rate.hip, profiles/r5v_valu_rate.json), so 16 mixes
@@ -188,33 +159,6 @@ __device__ __forceinline__ void split8_f16(const float* v, float s, uint4& hi, u
     float a0, a1, a2, a3, a4, a5, a6, a7, t0, t1, t2, t3, t4, t5, t6, t7;
     if constexpr (LEAD) asm("s_nop 7\n\t" SAMNERF_SPLIT8_ASM : SAMNERF_SPLIT8_OUT : SAMNERF_SPLIT8_IN);
     else asm(SAMNERF_SPLIT8_ASM : SAMNERF_SPLIT8_OUT : SAMNERF_SPLIT8_IN);
-    hi = make_uint4(h0, h1, h2, h3);
-    lo = make_uint4(l0, l1, l2, l3);
-}
-#else   // SAMNERF_SPLIT_MIX: rounds 1-5's v_fma_mix form (timing A/B)
-template <bool LEAD = false>   // timing variants: no leading pad
-__device__ __forceinline__ void split8_f16(const float* v, float s, uint4& hi, uint4& lo) {
-    uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
-    asm("v_fma_mixlo_f16 %0, %8, %16, 0\n\t"
-        "v_fma_mixlo_f16 %1, %10, %16, 0\n\t"
-        "v_fma_mixlo_f16 %2, %12, %16, 0\n\t"
-        "v_fma_mixlo_f16 %3, %14, %16, 0\n\t"
-        "v_fma_mixhi_f16 %0, %9, %16, 0\n\t"
-        "v_fma_mixhi_f16 %1, %11, %16, 0\n\t"
-        "v_fma_mixhi_f16 %2, %13, %16, 0\n\t"
-        "v_fma_mixhi_f16 %3, %15, %16, 0\n\t"
-        "v_fma_mixlo_f16 %4, %8, %16, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %5, %10, %16, -%1 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %6, %12, %16, -%2 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %7, %14, %16, -%3 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %4, %9, %16, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %5, %11, %16, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %6, %13, %16, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %7, %15, %16, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-        : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]),
-          "v"(s));
     hi = make_uint4(h0, h1, h2, h3);
     lo = make_uint4(l0, l1, l2, l3);
 }

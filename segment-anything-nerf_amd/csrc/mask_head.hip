@@ -47,16 +47,9 @@ constexpr int kHkb = 16;                      // 256 -> 16 k-blocks
 constexpr int kStepsPerSample = kL0kb + kHkb + 2;   // 27
 constexpr int kStepVec = 2 * 8 * 64;          // uint4 per step
 constexpr int kSlots = 128;                   // ray slots per workgroup
-constexpr int kPackVec = kStepsPerSample * kStepVec;   // uint4 of one copy of the weight fragments
-// Copies of the fragments: every workgroup streams the same steps at about
-// the same time; workgroup b reads copy (b >> 3) % kMaskCopies so that each
-// XCD's requests spread over that many times as many L2 channels (the
-// SAM head's kHeadCopies).  The copies hold the same bits.  Measured no
-// faster (9.13 vs 9.04 ms per mask view with the VGPR-staged stream), so one.
-#ifndef SAMNERF_MASK_COPIES
-#define SAMNERF_MASK_COPIES 1
-#endif
-constexpr int kMaskCopies = SAMNERF_MASK_COPIES;
+constexpr int kPackVec = kStepsPerSample * kStepVec;   // uint4 of the weight fragments
+// One copy.  Several, read by workgroup (b >> 3) % copies to spread a step's
+// requests over more L2 channels, measured no faster (9.13 vs 9.04 ms per mask view).
 constexpr int kT = 32;                        // final samples per ray
 __device__ __forceinline__ int rho(int q) { return (q & 3) + 8 * (q >> 2); }
 __device__ __forceinline__ int hidden_unit(int kb, int h, int m) {
@@ -130,11 +123,8 @@ k_mask_pack_f32(const float* __restrict__ w0, const float* __restrict__ w1, cons
     for (int m = 0; m < 8; ++m) v[m] = mask_weight(w0, w1, w2, K, step, slot, lane, m);
     uint4 a, b;
     to_operand<true>(v, 1.0f, a, b);
-#pragma unroll
-    for (int c = 0; c < kMaskCopies; ++c) {
-        packed[(size_t)c * kPackVec + (size_t)step * kStepVec + slot * 64 + lane] = a;
-        packed[(size_t)c * kPackVec + (size_t)step * kStepVec + 512 + slot * 64 + lane] = b;
-    }
+    packed[(size_t)step * kStepVec + slot * 64 + lane] = a;
+    packed[(size_t)step * kStepVec + 512 + slot * 64 + lane] = b;
 }
 
 // f16x3 weights (head_mode 0): one workgroup finds each tensor's max |w|, then
@@ -172,13 +162,11 @@ k_mask_pack_h16(const float* __restrict__ w0, const float* __restrict__ w1, cons
         for (int m = 0; m < 8; ++m) v[m] = mask_weight(w0, w1, w2, K, step, slot, lane2, m);
         uint4 a, b;
         to_operand<false>(v, exp2i(ke[step_layer(step)]), a, b);
-#pragma unroll
-        for (int c = 0; c < kMaskCopies; ++c) {
-            packed[(size_t)c * kPackVec + (size_t)step * kStepVec + slot * 64 + lane2] = a;
-            packed[(size_t)c * kPackVec + (size_t)step * kStepVec + 512 + slot * 64 + lane2] = b;
-        }
+        uint4* const dst = packed + (size_t)step * kStepVec + slot * 64 + lane2;
+        dst[0] = a;
+        dst[512] = b;
     }
-    if (tid < 3) reinterpret_cast<int*>(packed + (size_t)kMaskCopies * kPackVec)[tid] = ke[tid];
+    if (tid < 3) reinterpret_cast<int*>(packed + kPackVec)[tid] = ke[tid];
 }
 
 struct MaskArgs {
@@ -191,72 +179,6 @@ struct MaskArgs {
     const uint4* packed;
     const int* kexp;         // f16x3: the three weight tensors' log2 scales
     float* out;              // [N][K] (ray order)
-};
-
-// The round-2/3 weight stream (SAMNERF_MASK_RING=0 builds only), staged
-// through VGPRs: steps go in groups of kGroup; the block's 256 threads load the
-// next group (kGroup x 16 KiB, four 16-B loads per thread and step) at the
-// start of a group, write it to the other half of a 2-group LDS ring after the
-// group's MFMAs, then one barrier per group.  (Round 2: a dword LDS-DMA ring
-// measured slower than this form; two steps per group spilled 52-93 VGPRs.)
-constexpr uint32_t kGroup = 1;
-struct MaskStager {
-    const uint4* __restrict__ packed;
-    uint4* Wb;            // [2][kGroup][kStepVec]
-    int tid, lane;
-    uint32_t step;
-    uint32_t total;
-    uint4 stg[4 * kGroup];
-
-    __device__ __forceinline__ void load(uint32_t g) {          // group g = steps g kGroup ..
-#pragma unroll
-        for (uint32_t i = 0; i < kGroup; ++i) {
-            const uint32_t s = g * kGroup + i;
-            const uint4* src = packed + (size_t)(s % kStepsPerSample) * kStepVec + tid;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) stg[4 * i + c] = s < total ? src[c * 256] : make_uint4(0, 0, 0, 0);
-        }
-    }
-    __device__ __forceinline__ void store(uint32_t g) {
-        uint4* dst = Wb + (size_t)(g & 1u) * kGroup * kStepVec + tid;
-#pragma unroll
-        for (uint32_t i = 0; i < kGroup; ++i)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) dst[i * kStepVec + c * 256] = stg[4 * i + c];
-    }
-    __device__ __forceinline__ void begin() {
-        load(0);
-        store(0);
-        __syncthreads();
-    }
-    __device__ __forceinline__ const uint4* start() {
-        const uint32_t g = step / kGroup, i = step % kGroup;
-        if (i == 0 && (g + 1) * kGroup < total) load(g + 1);
-        return Wb + ((size_t)(g & 1u) * kGroup + i) * kStepVec + lane;
-    }
-    __device__ __forceinline__ void finish() {
-        const uint32_t g = step / kGroup, i = step % kGroup;
-        if (i == kGroup - 1 || step + 1 == total) {
-            if ((g + 1) * kGroup < total) store(g + 1);
-            __syncthreads();
-        }
-        ++step;
-    }
-
-    template <bool EXACT>
-    __device__ __forceinline__ void run8(floatx16 (&acc)[8], const uint4& b0, const uint4& b1) {
-        const uint4* cur = start();
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc[t] = kblock<EXACT>(cur[t * 64], cur[512 + t * 64], b0, b1, acc[t]);
-        finish();
-    }
-    template <bool EXACT>
-    __device__ __forceinline__ void run1(floatx16& acc, const uint4* b0, const uint4* b1) {
-        const uint4* cur = start();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc = kblock<EXACT>(cur[k * 64], cur[512 + k * 64], b0[k], b1[k], acc);
-        finish();
-    }
 };
 
 // The weight stream by LDS DMA (global_load_lds_dwordx4: 16 B per lane
@@ -274,12 +196,9 @@ struct MaskStager {
 // (LDS: 5 x 16 KiB ring + 4 x 18 KiB layer-0 operands).  Attribution builds of
 // the VGPR-staged form: without the m_grid gathers 7.92 ms, without the weight
 // loads 8.77, without the step barriers 8.63 -- the gathers at each sample's
-// start are the largest single stall.
-#ifndef SAMNERF_MASK_RING
-#define SAMNERF_MASK_RING 5
-#endif
-constexpr int kRing = SAMNERF_MASK_RING;
-static_assert(kRing == 0 || (kRing >= 3 && kRing <= 5), "finish() counts vmcnt for 3-5 deep rings");
+// start are the largest single stall.  So the ring is 5 deep and the
+// VGPR-staged stream (two-group LDS ring, one barrier per group) is gone.
+constexpr int kRing = 5;
 struct MaskStagerDma {
     const uint4* __restrict__ packed;
     uint4* Wb;            // [kRing][kStepVec]
@@ -321,9 +240,7 @@ struct MaskStagerDma {
     }
     __device__ __forceinline__ void finish() {
         if (step + kRing - 1 < total) {
-            if constexpr (kRing == 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if constexpr (kRing == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (kRing - 2)) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -445,23 +362,17 @@ k_mask_head(MaskArgs a) {
     // activations: with them the kernel spilled ~350 registers) | the m_grid
     // level descriptors (read per lane: a select between two kernel-argument
     // descriptors became per-lane loads from the kernarg segment)
-    constexpr uint32_t kRingUsed = kRing ? (uint32_t)kRing : 2u * kGroup;
-    __shared__ uint4 smem[kRingUsed * kStepVec + 4 * kXVec + kDescVec];
+    __shared__ uint4 smem[kRing * kStepVec + 4 * kXVec + kDescVec];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int j = lane & 31, h = lane >> 5;
     const uint32_t slot = blockIdx.x * kSlots + wave * 32u + j;
     const bool live = slot < a.N;
     const uint32_t ss = live ? slot : a.N - 1u, N = a.N;
-    uint4* const Xw = smem + kRingUsed * kStepVec + wave * kXVec;
-    LevelDesc* const sLv = reinterpret_cast<LevelDesc*>(smem + kRingUsed * kStepVec + 4 * kXVec);
+    uint4* const Xw = smem + kRing * kStepVec + wave * kXVec;
+    LevelDesc* const sLv = reinterpret_cast<LevelDesc*>(smem + kRing * kStepVec + 4 * kXVec);
     if (tid < 16) sLv[tid] = a.grid.lv[tid];
 
-    const uint4* const pk = a.packed + (size_t)((blockIdx.x >> 3) % kMaskCopies) * kPackVec;
-#if SAMNERF_MASK_RING
-    MaskStagerDma st{pk, smem, tid, lane, wave, 0u, (uint32_t)kT * kStepsPerSample};
-#else
-    MaskStager st{pk, smem, tid, lane, 0u, (uint32_t)kT * kStepsPerSample, {}};
-#endif
+    MaskStagerDma st{a.packed, smem, tid, lane, wave, 0u, (uint32_t)kT * kStepsPerSample};
     st.begin();
 
     floatx16 sum = {};                                       // sum_k w_k * logits_k
@@ -555,7 +466,7 @@ k_mask_head(MaskArgs a) {
 }
 
 // ============================================ f16x3, 16-ray waves, 2 per SIMD
-// (round 6; SAMNERF_MASK_W8, the SAM head's k_sam_head_w8 structure applied
+// (round 6; the SAM head's k_sam_head_w8 structure applied
 // to the mask head).  k_mask_head holds 426 registers per
 // 32-ray wave, one wave per SIMD, so each sample's m_grid gathers and its
 // MFMAs run one after the other on every SIMD (the gathers were the largest
@@ -585,16 +496,13 @@ k_mask_head(MaskArgs a) {
 // (-3.5 %); 169 registers, no scratch.  Not the 2x two waves per SIMD could
 // give: the per-step barrier keeps a workgroup's 8 waves in lockstep, so the
 // two waves of a SIMD gather and multiply at the same time; two independent
-// 4-wave workgroups per CU (SAMNERF_MASK_W8=2) drift apart but must keep the
-// inputs in registers (no LDS for two rings and two input stages) and spill:
-// 9.1-9.2 ms.  Two levels' corner rows in flight instead of one: the same
+// 4-wave workgroups per CU drift apart but must keep the inputs in
+// registers (no LDS for two rings and two input stages) and spill: 9.1-9.2
+// ms, so that form is gone (WAVES stays a parameter, always 8).  Two levels' corner rows in flight instead of one: the same
 // time (200 registers); the next sample's gathers issued under this
 // sample's layer-1 MFMAs (software-pipelined into the free LDS input stage):
 // 7.55-7.59 against 7.44-7.53 ms (profiles/r6o_mask_pipe_ab.txt) -- the
 // gathers are not what bounds this form.
-#ifndef SAMNERF_MASK_W8
-#define SAMNERF_MASK_W8 1
-#endif
 namespace mw8 {
 constexpr int kRays = 16;                                      // ray slots per wave
 constexpr int kL0 = 5, kH = 8;                                   // layer-0 / hidden k-blocks (32 deep)
@@ -663,10 +571,10 @@ k_mask_pack_w8(const float* __restrict__ w0, const float* __restrict__ w1, const
     if (tid < 3) reinterpret_cast<int*>(packed + (size_t)S * kStepVec)[tid] = ke[tid];
 }
 
-template <int OT, int WAVES>
+template <int OT>
 struct MaskStreamW8 {
     static constexpr int S = mw8::steps(OT);
-    static constexpr int kPieces = 16 / WAVES;          // 1-KiB pieces per wave and step
+    static constexpr int kPieces = 2;                   // 1-KiB pieces per wave and step: 16 KiB over 8 waves
     const uint4* __restrict__ packed;
     uint4* Wb;            // [kNbuf][kStepVec]
     int wave, lane;
@@ -794,19 +702,15 @@ __device__ __forceinline__ int epilogue_w8(floatx4 (&acc)[16], uint4 (&ah)[mw8::
     return k;
 }
 
-// WAVES 8: one 512-thread workgroup per CU (128 ray slots), the layer-0
-// inputs through LDS.  WAVES 4: two independent 256-thread workgroups per CU
-// (64 slots each, its own weight ring and step barriers, the inputs in
-// registers): the two waves of a SIMD belong to different workgroups and
-// drift out of phase, so one's gathers run under the other's MFMAs, where the
-// 8 waves of one workgroup move in lockstep from barrier to barrier.
+// One 512-thread workgroup per CU (128 ray slots), the layer-0 inputs through
+// LDS; its 8 waves move in lockstep from barrier to barrier.
 template <int OT, int WAVES>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_mask_head_w8(MaskArgs a) {
-    // LDS: the weight ring | (WAVES 8) each wave's layer-0 inputs of the
-    // current sample (fp32, [k-block][part][lane]) | the level descriptors
-    constexpr bool XLDS = WAVES == 8;
-    constexpr int kXw = XLDS ? mw8::kL0 * 2 * 64 : 0;
+    static_assert(WAVES == 8, "the 4-wave form spilled and is retired");
+    // LDS: the weight ring | each wave's layer-0 inputs of the current sample
+    // (fp32, [k-block][part][lane]) | the level descriptors
+    constexpr int kXw = mw8::kL0 * 2 * 64;
     __shared__ uint4 smem[mw8::kNbuf * kStepVec + WAVES * kXw + kDescVec];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int j = lane & 15, g = lane >> 4;
@@ -816,7 +720,7 @@ k_mask_head_w8(MaskArgs a) {
     uint4* const Xw = smem + mw8::kNbuf * kStepVec + wave * kXw;
     LevelDesc* const sLv = reinterpret_cast<LevelDesc*>(smem + mw8::kNbuf * kStepVec + WAVES * kXw);
     if (tid < 16) sLv[tid] = a.grid.lv[tid];
-    MaskStreamW8<OT, WAVES> st{a.packed, smem, wave, lane, 0u, (uint32_t)kT * (uint32_t)mw8::steps(OT)};
+    MaskStreamW8<OT> st{a.packed, smem, wave, lane, 0u, (uint32_t)kT * (uint32_t)mw8::steps(OT)};
     st.begin();
 
     const int kw = a.kexp[0] + a.kexp[1] + a.kexp[2];             // the weight tensors' log2 scales
@@ -871,17 +775,11 @@ k_mask_head_w8(MaskArgs a) {
         f[0] = acc2[0].x, f[1] = acc2[0].y, f[2] = acc2[1].x, f[3] = acc2[1].y;
         f[4] = acc2[2].x, f[5] = acc2[2].y, f[6] = acc2[3].x, f[7] = acc2[3].y;
     };
-    float xr[XLDS ? 1 : mw8::kL0][8];                              // WAVES 4: the inputs in registers
     auto put = [&](int b, const float* f, float& xm) {
-        if constexpr (XLDS) {
-            Xw[(2 * b) * 64 + lane] = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]),
-                                                 __float_as_uint(f[2]), __float_as_uint(f[3]));
-            Xw[(2 * b + 1) * 64 + lane] = make_uint4(__float_as_uint(f[4]), __float_as_uint(f[5]),
-                                                     __float_as_uint(f[6]), __float_as_uint(f[7]));
-        } else {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) xr[b][m] = f[m];
-        }
+        Xw[(2 * b) * 64 + lane] = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]),
+                                             __float_as_uint(f[2]), __float_as_uint(f[3]));
+        Xw[(2 * b + 1) * 64 + lane] = make_uint4(__float_as_uint(f[4]), __float_as_uint(f[5]),
+                                                 __float_as_uint(f[6]), __float_as_uint(f[7]));
 #pragma unroll
         for (int m = 0; m < 8; ++m) xm = fmaxf(xm, fabsf(f[m]));
     };
@@ -925,16 +823,10 @@ k_mask_head_w8(MaskArgs a) {
         for (int t = 0; t < 16; ++t) acc[t] = floatx4{};
 #pragma unroll
         for (int b = 0; b < mw8::kL0; ++b) {
-            float v[8];
-            if constexpr (XLDS) {
-                const uint4 u0 = Xw[(2 * b) * 64 + lane], u1 = Xw[(2 * b + 1) * 64 + lane];
-                v[0] = __uint_as_float(u0.x), v[1] = __uint_as_float(u0.y), v[2] = __uint_as_float(u0.z);
-                v[3] = __uint_as_float(u0.w), v[4] = __uint_as_float(u1.x), v[5] = __uint_as_float(u1.y);
-                v[6] = __uint_as_float(u1.z), v[7] = __uint_as_float(u1.w);
-            } else {
-#pragma unroll
-                for (int m = 0; m < 8; ++m) v[m] = xr[b][m];
-            }
+            const uint4 u0 = Xw[(2 * b) * 64 + lane], u1 = Xw[(2 * b + 1) * 64 + lane];
+            const float v[8] = {__uint_as_float(u0.x), __uint_as_float(u0.y), __uint_as_float(u0.z),
+                                __uint_as_float(u0.w), __uint_as_float(u1.x), __uint_as_float(u1.y),
+                                __uint_as_float(u1.z), __uint_as_float(u1.w)};
             uint4 xh, xl;
             split8_f16<true>(v, s0, xh, xl);
             st.template run<0>(acc, xh, xl);
@@ -976,7 +868,7 @@ k_mask_head_w8(MaskArgs a) {
 namespace samnerf {
 
 size_t mask_head_packed_floats() {
-    const size_t h32 = (size_t)kMaskCopies * kPackVec * 4 + 4;
+    const size_t h32 = (size_t)kPackVec * 4 + 4;
     const size_t hw8 = (size_t)mw8::steps(2) * kStepVec * 4 + 4;             // k_mask_head_w8's steps
     return h32 > hw8 ? h32 : hw8;
 }
@@ -995,17 +887,16 @@ int mask_head_forward(const samnerf_model* m, const GridDesc<16>& grid, const fl
     a.K = m->mask_out;
     a.tiles = tiles;
     a.packed = pk;
-    a.kexp = reinterpret_cast<const int*>(pk + (size_t)kMaskCopies * kPackVec);
+    a.kexp = reinterpret_cast<const int*>(pk + kPackVec);
     a.out = out;
     if (m->head_mode == 1) {
         k_mask_pack_f32<<<div_up(nfrag, 256), 256, 0, s>>>(m->mask_w[0], m->mask_w[1], m->mask_w[2],
                                                            m->mask_out, pk);
         k_mask_head<true><<<div_up(N, (uint32_t)kSlots), 256, 0, s>>>(a);
-    } else if (SAMNERF_MASK_W8 && N < (1u << 21)) {
-        // 1: one 8-wave workgroup per CU (7.57-7.60 ms per mask view against
-        // 7.86-7.94 for k_mask_head, profiles/r6m_mask_w8_ab.txt); 2: two
-        // 4-wave workgroups per CU (the inputs in registers spill: 9.1-9.2 ms)
-        constexpr int W = SAMNERF_MASK_W8 == 2 ? 4 : 8;
+    } else if (N < (1u << 21)) {
+        // one 8-wave workgroup per CU (7.57-7.60 ms per mask view against
+        // 7.86-7.94 for k_mask_head, profiles/r6m_mask_w8_ab.txt)
+        constexpr int W = 8;
         const uint32_t grid = div_up(N, (uint32_t)(W * mw8::kRays));
         if (m->mask_out > 16u) {
             k_mask_pack_w8<2><<<1, 1024, 0, s>>>(m->mask_w[0], m->mask_w[1], m->mask_w[2], m->mask_out, pk);

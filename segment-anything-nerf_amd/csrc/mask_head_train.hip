@@ -284,13 +284,7 @@ __device__ __forceinline__ void mt_scatter(const BwdArgs& a, const LevelDesc* sL
     // consecutive rows fall in the same cell: a lane keeps adding to its
     // corner row while the row repeats and sends one atomic per run.
     const int c = lane >> 3, ch = lane & 7;
-#ifdef SAMNERF_AB_MT_NOSCATTER   // timing attribution only: no m_grid gradient
-    return;
-#endif
     for (int l = w; l < 16; l += 4) {
-#ifdef SAMNERF_AB_MT_SCATTER_LEVELS   // timing attribution only: scatter levels [lo, hi) only
-        if (l < (SAMNERF_AB_MT_SCATTER_LEVELS >> 8) || l >= (SAMNERF_AB_MT_SCATTER_LEVELS & 255)) continue;
-#endif
         float* const tgt = (uint32_t)l < a.rep_levels ? a.rep + (blockIdx.x & (kRep - 1u)) * a.rep_floats : a.gemb;
         uint32_t run = 0xffffffffu;                           // the lane's current corner row (byte offset)
         float acc = 0.0f;

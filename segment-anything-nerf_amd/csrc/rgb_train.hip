@@ -585,11 +585,7 @@ k_rt_final_bwd(RtArgs a) {
         if (live) a.dh2[i * S + s] = g2[i];
     }
     float g1[64];
-#ifdef RT_BWD_G1_UNROLL   // diagnostics: g1 in registers (fully unrolled) instead of scratch
-#pragma unroll
-#else
 #pragma unroll 4
-#endif
     for (int i = 0; i < 64; ++i) {
         float acc = 0.0f;
 #pragma unroll
@@ -606,9 +602,6 @@ k_rt_final_bwd(RtArgs a) {
             df0 = __builtin_fmaf(sw[q * 32 + 2 * l], g1[q], df0);
             df1 = __builtin_fmaf(sw[q * 32 + 2 * l + 1], g1[q], df1);
         }
-#ifdef RT_DIAG_LMASK   // diagnostics only (tools/diag): scatter a subset of the levels
-        if (!((RT_DIAG_LMASK >> l) & 1)) continue;
-#endif
         scatter_level_c2(level_table(a.grad_grid, a.grad_rep, a.rep_levels, a.rep_floats, l), a.grid.lv[l], ux,
                          uy, uz, df0, df1, live, stage);
     }
@@ -970,9 +963,6 @@ __global__ void __launch_bounds__(256) k_rt_prop_bwd(PropBwdArgs a) {
     }
 #pragma unroll
     for (int l = 0; l < 5; ++l)
-#ifdef RT_DIAG_PMASK   // diagnostics only (tools/diag)
-        if ((RT_DIAG_PMASK >> l) & 1)
-#endif
         scatter_level_c2(level_table(a.grad_grid, a.grad_rep, a.rep_levels, a.rep_floats, l), a.grid.lv[l], ux,
                          uy, uz, df[2 * l], df[2 * l + 1], live, stage);
     // the prop_mlp weight gradients dP0 = sum dh f^T, dP1 = sum dx h^T: wave

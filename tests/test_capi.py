@@ -64,6 +64,35 @@ def test_argument_errors_return_codes_and_messages(hip_lib):
     assert rc == -1
     # zero-size work is a successful no-op (no launch)
     assert L.samnerf_grid_encode_forward(p, p, p, p, 0, 3, 2, 16, 16, 0.5, 16, None, 0, 0, 0, None) == 0
+    # the diagnostic build refuses a SAM-head form it does not hold (a retired
+    # one, or text atoi would read as 0) before it launches anything
+    from samnerf_amd import _lib
+    m = _lib.SamnerfModel()
+    m.with_sam = 1
+    for i in range(5):
+        m.sam_w[i] = m.sam_b[i] = 64
+    m.ln_w = m.ln_b = 64
+    need = L.samnerf_sam_head_workspace_size()
+    try:
+        with _lib.diag_library() as D:
+            for bad in ("4", "21", "0x", ""):
+                os.environ["SAMNERF_HEAD_V"] = bad
+                assert D.samnerf_sam_head_forward(ctypes.byref(m), p, 1, p, p, need, None) == -1
+                assert b"SAMNERF_HEAD_V must be 0, 30 or 31" in D.samnerf_last_error()
+    finally:
+        os.environ.pop("SAMNERF_HEAD_V", None)
+
+
+def test_sam_head_workspace_size_is_the_w8_packing(hip_lib):
+    """88 steps of 16 KiB fragments, 8 ints of log2 scales, 5 x 32 partial
+    maxima: the largest of the head forms' packings, in both builds (the
+    value before the superseded forms were retired)."""
+    from samnerf_amd import _lib
+    want = (88 * 1024 * 4 + 8 + 5 * 32) * 4
+    assert want == 1442464
+    assert hip_lib.samnerf_sam_head_workspace_size() == want
+    with _lib.diag_library() as D:
+        assert D.samnerf_sam_head_workspace_size() == want
 
 
 def test_render_workspace_size_scales_with_rays(hip_lib):

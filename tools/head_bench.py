@@ -5,9 +5,12 @@ Runs samnerf_sam_head_forward on N random head-input rows (the [N, 164] rows
 k_final writes) with the default-architecture head (163 -> 256 x 5 +
 LayerNorm), times it with HIP events over --iters launches, and checks:
   * every diagnostic variant listed in --variants (SAMNERF_HEAD_V=<v>, read by
-    libsamnerf_hip_diag.so only) is bit-identical to the product library;
+    libsamnerf_hip_diag.so only) against the product library: 0 = the 32-ray
+    k_sam_head_h16q, 31 = two 4-wave k_sam_head_w8 workgroups per CU (30 is
+    the product itself; any other value is refused).  Both are
+    fp32-equivalent to the product; only 31 is bit-identical to it;
   * the product head against the exact-fp32 MFMA head (head_mode 1).
-usage (GPU box): python tools/head_bench.py [--n 262144] [--variants 0,1]
+usage (GPU box): python tools/head_bench.py [--n 262144] [--variants 0,31]
 """
 import argparse
 import json

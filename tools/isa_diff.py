@@ -7,7 +7,8 @@ are pooled by symbol across the files of a directory, so a kernel that moved
 to another translation unit still meets its counterpart.  Per symbol the
 instruction lines are compared -- comments stripped, blank lines and
 assembler directives dropped, the per-function label numbers .LBB<n>_
-normalised to .LBB_ -- and, for kernels, the resource record of the
+normalised to .LBB_ and the module-wide numbers of the long-branch labels
+.Lpost_getpc<n> dropped -- and, for kernels, the resource record of the
 metadata: .vgpr_count, .agpr_count, .sgpr_count, the spill counts,
 .group_segment_fixed_size, .private_segment_fixed_size.
 
@@ -33,9 +34,9 @@ def normalise(body):
     out = []
     for line in body:
         line = line.split(";", 1)[0].strip()
-        if not line or (line.startswith(".") and not line.startswith(".LBB")):
+        if not line or (line.startswith(".") and not line.startswith((".LBB", ".Lpost_getpc"))):
             continue
-        out.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+        out.append(re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", line)))
     return out
 
 
