@@ -275,17 +275,47 @@ typedef struct {
     uint64_t perturb_offset;
 } samnerf_model;
 
+/* The reference's --background modes and bg_color shapes, for the NEXT calls of
+ * this thread (like samnerf_set_taps; samnerf_model keeps its layout -- its last
+ * fields stay the perturb_* ones).
+ * background: 0 = 'last_sample' (the default: the last sample's delta * sigma is
+ * +inf in every compositing, renderer.py:314, so weights_sum is 1); 1 =
+ * transparent ('white' and 'random': that line is skipped, the last sample
+ * composites like any other and weights_sum <= 1).
+ * bg_rgb: device pointer, [n_bg,3] floats in ray order; NULL = the scalar bg_color
+ * argument (samnerf_rgb_train_opts.bg_color for samnerf_rgb_train_step, which
+ * bg_rgb overrides).  n_bg = 1: one colour for every ray (the GUI's [3] colour);
+ * n_bg = N: a colour per ray (training under --background random,
+ * utils.py:892-896).  No gradient is produced for the colour.
+ * samnerf_set_background(NULL) restores the defaults (0, NULL, 0); it only stores
+ * the values.  They are validated beside the other arguments of every call that
+ * reads them -- samnerf_render_forward, _forward_tile, samnerf_rgb_train_step,
+ * _forward and _backward: background not in {0, 1}, bg_rgb != NULL with n_bg not
+ * in {1, N}, or bg_rgb == NULL with n_bg != 0 is SAMNERF_EINVAL, the message naming
+ * the field.  The setting stays until it is set again: set it before a call and
+ * restore the defaults after it.  samnerf_rgb_train_backward must run under the
+ * forward's setting (the bg_rgb buffer still holding the forward's values). */
+typedef struct {
+    int background;
+    const float* bg_rgb;
+    uint32_t n_bg;
+} samnerf_background;
+int samnerf_set_background(const samnerf_background* bg);
+
 /* Bytes of device workspace samnerf_render_forward needs for N rays. */
 size_t samnerf_render_workspace_size(const samnerf_model* model, uint32_t N);
 
 /* The whole ray-march inner loop for N rays (NeRFRenderer.run in eval mode:
- * perturb = False unless model->perturb or model->perturb_device is set, background 'last_sample', sum_after_mlp = False,
+ * perturb = False unless model->perturb or model->perturb_device is set, background 'last_sample' or transparent by samnerf_set_background, sum_after_mlp = False,
  * sam_use_view_direction = True): near/far, 3 proposal rounds with
  * inverse-CDF resampling, hash-grid + SH encoding, sigma / colour MLPs,
  * compositing, view MLP, and (with_sam) the s_grid feature composite plus the
  * SkipConnMLP + LayerNorm head.
  *   rays_o, rays_d [N,3]; cam_near_far [N,2] or [1,2] (n_cnf rows) or NULL;
- *   bg_color: scalar background (renderer.py:239-240, default 1);
+ *   bg_color: scalar background (renderer.py:239-240, default 1), used when
+ *   no bg_rgb is set (samnerf_set_background); bg_rgb [n_bg,3]: one RGB colour (n_bg = 1) or
+ *   one per ray (n_bg = N), mixed in as (1 - weights_sum) * colour
+ *   (renderer.py:356) -- also in the image columns of feature_rows;
  *   image [N,3], depth [N], weights_sum [N]; samvit [N,256] (with_sam; NULL
  *   = features not wanted: the s_grid composite and the head are skipped --
  *   renderer.py computes and drops them when return_feats == 0);
@@ -469,7 +499,7 @@ typedef struct {
     float lambda_distort;         /* main.py:108, default 0.02 */
     float lambda_entropy;         /* main.py:100, default 0 */
     int update_proposal;          /* utils.py:912-913 */
-    float bg_color;               /* scalar background (1 for 'last_sample') */
+    float bg_color;               /* scalar background (1 for 'last_sample'); a set bg_rgb overrides it */
 } samnerf_rgb_train_opts;
 typedef struct {
     float* grid;                  /* grid.embeddings [rows,2] */

@@ -35,6 +35,24 @@ int check_perturb(const samnerf_model* m, const char* what, bool all_or_none) {
     return SAMNERF_OK;
 }
 
+// samnerf_set_background's values of this thread (defaults: 'last_sample', scalar colour)
+static thread_local samnerf_background g_bg = {0, nullptr, 0u};
+
+const samnerf_background& current_background() { return g_bg; }
+
+int check_background(uint32_t N, const char* what) {
+    const samnerf_background* m = &g_bg;
+    if (m->background != 0 && m->background != 1)
+        return fail(SAMNERF_EINVAL, "%s: background %d is neither 0 ('last_sample') nor 1 (transparent)", what,
+                    m->background);
+    if (m->bg_rgb && m->n_bg != 1u && m->n_bg != N)
+        return fail(SAMNERF_EINVAL, "%s: bg_rgb needs n_bg = 1 or N = %u rows (got n_bg = %u)", what, N, m->n_bg);
+    if (!m->bg_rgb && m->n_bg != 0u)
+        return fail(SAMNERF_EINVAL, "%s: n_bg = %u with a null bg_rgb (NULL: the scalar bg_color, n_bg = 0)", what,
+                    m->n_bg);
+    return SAMNERF_OK;
+}
+
 ResTable make_res_table(uint32_t L, float S, uint32_t H) {
     ResTable t;
     for (uint32_t l = 0; l < 32; ++l) {
@@ -83,6 +101,11 @@ int samnerf_diag_variants(void) {
 }
 
 const char* samnerf_last_error(void) { return samnerf::g_err; }
+
+int samnerf_set_background(const samnerf_background* bg) {
+    samnerf::g_bg = bg ? *bg : samnerf_background{0, nullptr, 0u};
+    return SAMNERF_OK;
+}
 
 // torch.linspace on the CPU for float32 (ATen RangeFactoriesKernel): step in
 // float, the first half fma(step, i, start), the second half

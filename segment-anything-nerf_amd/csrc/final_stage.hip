@@ -22,7 +22,7 @@ struct FinalArgs {
     const float* rays_d;
     uint32_t N;
     GridScale gs;
-    float bg;
+    float bg;               // scalar background, used when bg_rgb (below) is null
     // The main grid's level descriptors by value (kernarg), copied into LDS
     // at kernel start; each half-wave reads its slot's descriptor from there.
     // Round 1 read them from a copy in the workspace (written by a one-thread
@@ -100,6 +100,11 @@ struct FinalArgs {
     float* sigma_tap;
     uint32_t* rows_tap;
     uint32_t tap_stride;
+    // samnerf_set_background's background / bg_rgb / n_bg (appended: the arguments above
+    // keep their kernarg offsets)
+    uint32_t last_inf;      // 1: 'last_sample' (the last sample's ds is +inf), 0: transparent
+    uint32_t n_bg;          // rows of bg_rgb: 1 (one colour) or N (per ray)
+    const float* bg_rgb;    // [n_bg][3] in ray order, or null: the scalar bg
 };
 
 // ---- grid_mlp on f16x3 MFMAs (v_mfma_f32_32x32x16_f16, fp32 accumulate).
@@ -442,6 +447,10 @@ k_final(FinalArgs a) {
     }
 
     int exit_at = i_end;                                  // EXIT: first step not marched
+    // 'last_sample': the last sample's delta * sigma is +inf (renderer.py:314);
+    // transparent: no sample's is (k_inf = -1).  Wave-uniform, from a kernel
+    // argument: a scalar register compared in place of the constant T - 1.
+    const int k_inf = a.last_inf ? T - 1 : -1;
     for (int i = i_begin; i < i_end; ++i) {
         const int k = i * S + seg;
         float rb_next, ux, uy, uz;
@@ -640,7 +649,7 @@ k_final(FinalArgs a) {
         const float sigma = expf(s_lo);
         // composite (renderer.py:300-307): w_k = alpha_k * exp(-sum_{j<k} ds_j),
         // the sum in double and in sample order across the ray's S slots
-        const float ds = k == T - 1 ? INFINITY : (rb_next - rb_prev) * sigma;
+        const float ds = k == k_inf ? INFINITY : (rb_next - rb_prev) * sigma;
         double before = cum;
 #pragma unroll
         for (int s2 = 0; s2 < S; ++s2) {
@@ -849,9 +858,18 @@ k_final(FinalArgs a) {
     }
     if (hh != 0) return;
     float img[3];
+    // the background colour of this RAY (not slot: view_width tiling permutes
+    // them): one colour for all (n_bg = 1), one per ray, or the scalar
+    const float* bgp = a.bg_rgb ? a.bg_rgb + (size_t)(a.n_bg == 1u ? 0u : ray) * 3 : nullptr;
+    // the scalar as a value before the choice: `bgp ? bgp[c] : a.bg` becomes
+    // one load through a select of the two ADDRESSES, the argument struct's
+    // own among them, and the whole struct is then copied to scratch (~900
+    // bytes per lane in every form of the kernel)
+    const float bg0 = a.bg;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {                // rows 0..2 of v3 = registers 0..2, lower half
-        img[c] = sigmoidf(SA ? rgb[c] : v3[c]) + (1.0f - ws) * a.bg;
+        const float bg_c = bgp ? bgp[c] : bg0;
+        img[c] = sigmoidf(SA ? rgb[c] : v3[c]) + (1.0f - ws) * bg_c;
         a.image[(size_t)ray * a.img_ld + c] = img[c];
     }
     a.depth[(size_t)ray * a.scal_ld] = dp;
@@ -1144,6 +1162,9 @@ int run_final(const samnerf_model* m, uint32_t N, const FinalRun& r, const Works
     fa.tiles = r.tiles;
     fa.gs = make_grid_scale(m->grid_bound);
     fa.bg = r.bg;
+    fa.bg_rgb = r.bg_rgb;
+    fa.n_bg = r.n_bg;
+    fa.last_inf = current_background().background == 0 ? 1u : 0u;
     fa.grid = r.grid;
     fa.grid_emb = r.grid.emb;
     const GridDesc<16>& gg = r.grid;

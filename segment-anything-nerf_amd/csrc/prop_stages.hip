@@ -92,6 +92,11 @@ struct PropArgs {
     // perturb=True drawn in the kernels (samnerf_model.perturb_device, philox.h):
     // read by the seeded kernel forms only (PHX), which take neither array above
     PerturbKey phx;
+    // from samnerf_set_background: 1 under 'last_sample' (the last sample's
+    // delta * sigma is +inf, renderer.py:314), 0 under the transparent modes (it
+    // composites like any other); wave-uniform, read once before the
+    // compositing loops
+    uint32_t last_inf;
 };
 
 // Bin i of a stage's input for slot r (ray `ray`): stage 0 linspace(0, 1, T+1)
@@ -416,8 +421,13 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
     __shared__ uint32_t qwin[4][64];          // and its SumWindow
     const bool rl = lane < nr;
     const int k0 = (int)part * Q;
-    // A1: ds quarter sums (the last sample's ds is replaced by +inf and the
-    // sum after it is never read: not part of the window)
+    const int k_inf = a.last_inf ? T - 1 : -1;            // the sample whose ds is +inf (uniform)
+    // A1: ds quarter sums.  The last sample's ds is never part of the window
+    // or of a quarter sum, in either background mode: 'last_sample' replaces
+    // it by +inf, the transparent modes composite it as it is, and in both it
+    // only enters the sample's own alpha -- the running sum is read before
+    // each sample (composite_step), so the sum after the last one is never
+    // read and the exact-sum argument covers the same T - 1 terms
     {
         SumWindow win;
         double q = 0.0;
@@ -442,11 +452,11 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
             double cum = 0.0;
             for (int p = 0; p < (int)part; ++p) cum += qsum[p][lane];
 #pragma unroll 8
-            for (int k = k0; k < k0 + Q; ++k) row[k] = composite_step(row[k], cum, k == T - 1);
+            for (int k = k0; k < k0 + Q; ++k) row[k] = composite_step(row[k], cum, k == k_inf);
         } else if (part == 0) {
             double cum = 0.0;
 #pragma unroll 8
-            for (int k = 0; k < T; ++k) row[k] = composite_step(row[k], cum, k == T - 1);
+            for (int k = 0; k < T; ++k) row[k] = composite_step(row[k], cum, k == k_inf);
         }
     }
     __syncthreads();
@@ -516,8 +526,9 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
         // unrolled by 8: the LDS reads run ahead of the double-precision
         // chains (a full unroll takes 248 VGPRs and halves occupancy)
         double cum = 0.0;
+        const int k_inf = a.last_inf ? T - 1 : -1;
 #pragma unroll 8
-        for (int k = 0; k < T; ++k) row[k] = composite_step(row[k], cum, k == T - 1);
+        for (int k = 0; k < T; ++k) row[k] = composite_step(row[k], cum, k == k_inf);
         if (a.w_out)
             for (int k = 0; k < T; ++k) a.w_out[(size_t)k * N + r0 + lane] = row[k];
         const float wsum = torch_row_sum(T, [&](int i) { return row[i] + 0.01f; });
@@ -879,6 +890,7 @@ void run_proposal_stages(const samnerf_model* m, uint32_t N, const ProposalRun& 
     pa.gs = make_grid_scale(m->grid_bound);
     pa.snf = r.snf;
     pa.rec = r.rec;
+    pa.last_inf = current_background().background == 0 ? 1u : 0u;
     // SAMNERF_PROP_FUSED=1: one kernel per proposal stage, ds kept in LDS
     // (k_prop_fused; bit-identical, but measured 1.9x slower -- prop0 1.10 vs
     // 0.59 ms per view -- so the two-kernel form stays the default)

@@ -387,6 +387,7 @@ int render_impl(const samnerf_model* m, const float* rays_o, const float* rays_d
     if (cam_near_far && n_cnf != 1 && n_cnf != N)
         return fail(SAMNERF_EINVAL, "render: cam_near_far must have 1 or N rows");
     if (int prc = check_perturb(m, "render")) return prc;
+    if (int brc = check_background(N, "render")) return brc;
     Workspace w = carve(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "render: workspace needs %zu bytes, got %zu", w.bytes,
@@ -448,6 +449,8 @@ int render_impl(const samnerf_model* m, const float* rays_o, const float* rays_d
     fr.grid = gg;
     fr.bins_in = bins2;
     fr.bg = bg_color;
+    fr.bg_rgb = current_background().bg_rgb;
+    fr.n_bg = current_background().n_bg;
     fr.image = image;
     fr.depth = depth;
     fr.wsum = weights_sum;

@@ -156,7 +156,9 @@ struct FinalRun {
     RayTiles tiles;
     GridDesc<16> grid;       // the main grid, L16 C2
     const float* bins_in;    // [33][N]
-    float bg;
+    float bg;                // scalar background, or
+    const float* bg_rgb;     // [n_bg][3] colours in ray order (samnerf_set_background), n_bg 1 or N
+    uint32_t n_bg;
     float* image;            // per-ray outputs, ray order (FinalArgs)
     float* depth;
     float* wsum;

@@ -129,7 +129,20 @@ struct RtArgs {
     float* grad_grid;         // [rows][2]
     float* grad_rep;          // [kRep][rep_floats]: the coarse levels' gradient, one copy per XCD
     uint32_t rep_levels, rep_floats;
+    // samnerf_set_background's background / bg_rgb / n_bg (wave-uniform):
+    uint32_t last_inf;        // 1: 'last_sample' (the last sample's delta * sigma is +inf), 0: transparent
+    uint32_t n_bg;            // rows of bg_rgb: 1 (one colour) or N (per ray)
+    const float* bg_rgb;      // [n_bg][3] background colours, or null: the scalar bg
 };
+
+// Channel c of ray r's background colour (no gradient flows to it).
+// (The scalar is read as a value before the choice, so that the two loads
+// cannot merge into one through a select of addresses that takes the
+// argument struct's own: final_stage.hip's epilogue.)
+__device__ __forceinline__ float bg_of(const RtArgs& a, uint32_t r, uint32_t c) {
+    const float bg0 = a.bg;
+    return a.bg_rgb ? a.bg_rgb[(size_t)(a.n_bg == 1u ? 0u : r) * 3 + c] : bg0;
+}
 
 __device__ __forceinline__ float grid_u(const RtArgs& a, float x) {
     return a.inv_b2 != 0.0f ? (x + a.bound) * a.inv_b2 : (x + a.bound) / a.b2;
@@ -392,7 +405,7 @@ __device__ __forceinline__ V half_incl_suffix(V v, uint32_t k) {
 }
 
 // Compositing with one half-wave per ray (8 rays per block; renderer.py:309-358,
-// last_sample background, plus the per-ray distortion term): lane k
+// either background mode, plus the per-ray distortion term): lane k
 // composites sample k (the exclusive double cumsum of delta * sigma as a scan,
 // as composite_step orders it), the ray's sums are half-wave reductions, and
 // the view MLP runs unit-per-lane (v1 / v2 unit q on lane q).  (The first form,
@@ -405,8 +418,10 @@ __global__ void __launch_bounds__(256) k_rt_composite_h(RtArgs a) {
     const uint32_t r = r0;
     const size_t S = (size_t)kT * N, s = (size_t)r * kT + k, ks = (size_t)k * N + r;
     const bool last = k == (uint32_t)kT - 1u;
+    const bool inf = last && a.last_inf != 0u;             // 'last_sample': ds_31 = +inf (renderer.py:314)
     const float sigma = expf(a.out[s]);                    // trunc_exp forward
-    const float ds = last ? INFINITY : a.delta[s] * sigma;
+    const float ds = inf ? INFINITY : a.delta[s] * sigma;
+    // (the scan is read exclusively: the last sample's own ds reaches no sum)
     const double dsd = last ? 0.0 : (double)ds;
     const double cum = half_incl_scan(dsd, k) - dsd;       // before sample k
     const float w = nan_to_num((1.0f - expf(-ds)) * expf(-(float)cum));
@@ -453,7 +468,7 @@ __global__ void __launch_bounds__(256) k_rt_composite_h(RtArgs a) {
         const float zc = k == 0 ? z[0] : k == 1 ? z[1] : z[2];
         const float sg = sigmoidf(zc);
         a.sig[(size_t)k * N + r] = sg;
-        a.image[(size_t)r * 3 + k] = sg + (1.0f - ws) * a.bg;
+        a.image[(size_t)r * 3 + k] = sg + (1.0f - ws) * bg_of(a, r, k);
     }
     if (k == 0) {
         a.depth[r] = (float)dep;
@@ -474,11 +489,12 @@ __global__ void __launch_bounds__(256) k_rt_final_bwd_ray_h(RtArgs a) {
     if (r >= N) return;
     const size_t S = (size_t)kT * N, s = (size_t)r * kT + k, ks = (size_t)k * N + r;
     const bool last = k == (uint32_t)kT - 1u;
+    const bool inf = last && a.last_inf != 0u;             // as the forward
     float dimg[3], dz[3], dws = a.g_ws ? a.g_ws[r] : 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         dimg[c] = a.g_img[(size_t)r * 3 + c];
-        dws = dws - dimg[c] * a.bg;                         // image += (1 - weights_sum) * bg
+        dws = dws - dimg[c] * bg_of(a, r, (uint32_t)c);      // image += (1 - weights_sum) * bg
         const float sg = a.sig[(size_t)c * N + r];
         dz[c] = dimg[c] * (1.0f - sg) * sg;                 // sigmoid backward
     }
@@ -510,7 +526,7 @@ __global__ void __launch_bounds__(256) k_rt_final_bwd_ray_h(RtArgs a) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) g = __builtin_fmaf(dfi[15 + j], sh[j], g);   // d f_image[15:] / d w_k = sh
     // this sample: forward again, d(loss)/d(w_k)
-    const float ds = last ? INFINITY : a.delta[s] * expf(a.out[s]);
+    const float ds = inf ? INFINITY : a.delta[s] * expf(a.out[s]);
     const double dsd = last ? 0.0 : (double)ds;
     const double cum = half_incl_scan(dsd, k) - dsd;
     const float e = expf(-ds), Tk = expf(-(float)cum);
@@ -546,7 +562,7 @@ __global__ void __launch_bounds__(256) k_rt_final_bwd_ray_h(RtArgs a) {
     const double drd = fin ? (double)(dw * raw) : 0.0;
     const double after_k = half_incl_suffix(drd, k) - drd;
     float dx = 0.0f;
-    if (!last) {
+    if (!inf) {                                            // transparent: the last sample too (after_k = 0)
         const float dds = (float)((double)(dw * (e * Tk)) - after_k);
         const float x = a.out[s];
         dx = (dds * a.delta[s]) * expf(fminf(fmaxf(x, -15.0f), 15.0f));   // trunc_exp backward
@@ -749,6 +765,7 @@ struct PropBwdArgs {
     // stage 0, perturb drawn in the kernels (samnerf_model.perturb_device): the
     // seeded kernel forms (PHX) recompute the forward's bins from it (philox.h)
     PerturbKey phx;
+    uint32_t last_inf;        // as RtArgs
 };
 
 template <int T, bool FIRST, bool PHX = false>
@@ -861,6 +878,10 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
     if (lane == 0) a.terms[N + r] += loss / (float)kT;
     // dw1 = prefix of the difference array; the compositing forward again
     // (cum of ds in double, as the forward kernels) and the reverse scan
+    // ('last_sample': ds of the last sample is +inf and has no gradient;
+    // transparent: it is a sample like any other -- in both its own ds enters
+    // no running sum, which is read before each sample)
+    const int k_inf = a.last_inf ? T - 1 : -1;
     float dwl[E], dsl[E], dsum = 0.0f;
     double csum = 0.0;
 #pragma unroll
@@ -868,7 +889,7 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
         const int j = lane * E + e;
         dwl[e] = dd[j];
         dsum += dwl[e];
-        dsl[e] = j == T - 1 ? INFINITY : a.ds[(size_t)j * N + r];
+        dsl[e] = j == k_inf ? INFINITY : a.ds[(size_t)j * N + r];
         csum += j == T - 1 ? 0.0 : (double)dsl[e];
     }
     float dpre = wave_incl_scan(dsum, lane) - dsum;
@@ -892,7 +913,7 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
 #pragma unroll
     for (int e = E - 1; e >= 0; --e) {
         const int j = lane * E + e;
-        a.dds[(size_t)j * N + r] = j < T - 1 ? ev[e] - acc : 0.0f;
+        a.dds[(size_t)j * N + r] = j != k_inf ? ev[e] - acc : 0.0f;
         acc += raw[e];
     }
 }
@@ -1150,6 +1171,9 @@ int rt_setup(const samnerf_model* m, const float* rays_o, const float* rays_d, u
     a.b2 = c.geo.b2;
     a.inv_b2 = c.geo.inv_b2;
     a.bg = bg;
+    a.bg_rgb = current_background().bg_rgb;
+    a.n_bg = current_background().n_bg;
+    a.last_inf = current_background().background == 0 ? 1u : 0u;
     a.grid = c.geo.grid;
     for (int i = 0; i < 3; ++i) {
         a.G[i] = m->grid_mlp[i];
@@ -1189,6 +1213,7 @@ int rt_setup(const samnerf_model* m, const float* rays_o, const float* rays_d, u
     pb.bins0 = make_linspace(0.0f, 1.0f, 129);
     pb.pbins0 = m->perturb[0];
     pb.phx = make_perturb_key(m->perturb_seed, m->perturb_offset);
+    pb.last_inf = a.last_inf;
     pb.bins_in = w.p.bins1;
     pb.bins2 = w.p.bins2;
     pb.wf = a.w;
@@ -1315,6 +1340,7 @@ int samnerf_rgb_train_forward(const samnerf_model* m, const float* rays_o, const
     if (cam_near_far && n_cnf != 1 && n_cnf != N)
         return fail(SAMNERF_EINVAL, "rgb_train_forward: cam_near_far must have 1 or N rows");
     if (int prc = check_perturb(m, "rgb_train_forward")) return prc;
+    if (int brc = check_background(N, "rgb_train_forward")) return brc;
     RtWorkspace w = carve_rt(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "rgb_train_forward: workspace needs %zu bytes, got %zu", w.bytes,
@@ -1341,6 +1367,7 @@ int samnerf_rgb_train_backward(const samnerf_model* m, const float* rays_o, cons
     if (with_proposal && !grad_losses)
         return fail(SAMNERF_EINVAL, "rgb_train_backward: the proposal backward needs grad_losses");
     if (int prc = check_perturb(m, "rgb_train_backward", false)) return prc;
+    if (int brc = check_background(N, "rgb_train_backward")) return brc;
     RtWorkspace w = carve_rt(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "rgb_train_backward: workspace needs %zu bytes, got %zu", w.bytes,
@@ -1373,6 +1400,7 @@ int samnerf_rgb_train_step(const samnerf_model* m, const float* rays_o, const fl
     if (cam_near_far && n_cnf != 1 && n_cnf != N)
         return fail(SAMNERF_EINVAL, "rgb_train_step: cam_near_far must have 1 or N rows");
     if (int prc = check_perturb(m, "rgb_train_step")) return prc;
+    if (int brc = check_background(N, "rgb_train_step")) return brc;
     RtWorkspace w = carve_rt(m, N, workspace);
     if (!workspace || workspace_bytes < w.bytes)
         return fail(SAMNERF_EWORKSPACE, "rgb_train_step: workspace needs %zu bytes, got %zu", w.bytes,

@@ -35,6 +35,10 @@ int check_launch(const char* what);
 // samnerf_model's perturb sources: the position arrays all three or none
 // (all_or_none), and never together with perturb_device (philox.h)
 int check_perturb(const samnerf_model* m, const char* what, bool all_or_none = true);
+// samnerf_set_background's values of the calling thread, and their check for a
+// call over N rays
+const samnerf_background& current_background();
+int check_background(uint32_t N, const char* what);
 
 inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 

@@ -163,6 +163,8 @@ class NeRFRenderer(nn.Module):
             return self.run(rays_o, rays_d, cam_near_far=cam_near_far, **kwargs)
         N = rays_o.shape[0]
         H, W = kwargs.pop("H", None), kwargs.pop("W", None)
+        bg = kwargs.pop("bg_color", None)
+        per_ray_bg = torch.is_tensor(bg) and bg.dim() == 2 and bg.shape[0] == N and N != 1
         results = {}
         step = self.opt.max_ray_batch
         for head in range(0, N, step):
@@ -170,10 +172,14 @@ class NeRFRenderer(nn.Module):
             cnf = cam_near_far
             if cnf is not None and cnf.shape[0] != 1:
                 cnf = cnf[head:tail]
+            # a per-ray background [N,3] / [N,1] is sliced with the rays; a
+            # scalar or one [3] / [1,3] colour goes to every chunk
+            bgk = bg[head:tail] if per_ray_bg else bg
             # chunks of whole image rows keep the ray-tiling hint (W only: the
             # chunk's samvit stays flat)
             wk = W if (W is not None and step % W == 0) else None
-            part = self.run(rays_o[head:tail], rays_d[head:tail], cam_near_far=cnf, W=wk, **kwargs)
+            part = self.run(rays_o[head:tail], rays_d[head:tail], cam_near_far=cnf, W=wk, bg_color=bgk,
+                            **kwargs)
             for k, v in part.items():
                 if v is None:
                     continue
@@ -188,7 +194,23 @@ class NeRFRenderer(nn.Module):
             results["samvit"] = results["samvit"].view(H, W, -1)
         return results
 
-    def _fused_ok(self, rays_o, perturb, return_mask, kwargs):
+    @staticmethod
+    def _fused_bg_ok(bg_color, N):
+        """A background the fused kernels take: a number, a 1-element tensor,
+        one [3] / [1,3] colour or anything that broadcasts against [N,3] --
+        without gradient (none is produced for the colour)."""
+        if not torch.is_tensor(bg_color):
+            return True
+        if bg_color.requires_grad and torch.is_grad_enabled():
+            return False
+        from samnerf_amd.fused import bg_layout
+        try:
+            bg_layout(bg_color.detach(), N)
+        except ValueError:
+            return False
+        return True
+
+    def _fused_ok(self, rays_o, perturb, return_mask, kwargs, bg_color=None):
         if return_mask:
             from samnerf_amd.fused import mask_kind
             if mask_kind(self) is None:
@@ -199,7 +221,7 @@ class NeRFRenderer(nn.Module):
         train_ok = not self.training or (not torch.is_grad_enabled() and (
             self.opt.with_sam or getattr(self.opt, "with_mask", False)))
         return (self.fused and rays_o.is_cuda and train_ok
-                and self.opt.background == "last_sample"
+                and self._fused_bg_ok(bg_color, rays_o.shape[0])
                 # sum_after_mlp: RGB (+ mask) models on the fused path; with SAM
                 # the reference's branch crashes and run_torch raises
                 and not (getattr(self.opt, "sum_after_mlp", False) and self.opt.with_sam)
@@ -213,8 +235,8 @@ class NeRFRenderer(nn.Module):
         return (self.fused and rays_o.is_cuda and self.training and torch.is_grad_enabled()
                 and not o.with_sam and not getattr(o, "with_mask", False)
                 and not getattr(o, "sum_after_mlp", False) and not return_feats and not return_mask
-                and o.background == "last_sample" and list(o.num_steps) == [128, 64, 32]
-                and (not torch.is_tensor(bg_color) or bg_color.numel() == 1))
+                and list(o.num_steps) == [128, 64, 32]
+                and self._fused_bg_ok(bg_color, rays_o.shape[0]))
 
     def _fused_mask_train_ok(self, rays_o, bg_color, perturb, return_feats, return_mask):
         """Train mode under grad with return_mask=1 for a fused mask head --
@@ -229,10 +251,9 @@ class NeRFRenderer(nn.Module):
         return (mask_kind(self) is not None and self.fused and rays_o.is_cuda
                 and self.training and torch.is_grad_enabled() and not perturb
                 and not (getattr(o, "sum_after_mlp", False) and o.with_sam)
-                and o.background == "last_sample"
                 and list(o.num_steps) == [128, 64, 32]
                 and (not o.with_sam or o.sam_use_view_direction)
-                and (not torch.is_tensor(bg_color) or bg_color.numel() == 1))
+                and (not torch.is_tensor(bg_color) or (bg_color.numel() == 1 and not bg_color.requires_grad)))
 
     def _fused_perturb(self, perturb):
         """What a dispatched fused call gets as perturb=: the caller's value, or
@@ -261,7 +282,7 @@ class NeRFRenderer(nn.Module):
                 self._fused = FusedRenderer(self)
             return render_rgb_train(self._fused, rays_o, rays_d, cam_near_far, bg_color,
                                     self._fused_perturb(perturb), update_proposal)
-        if self._fused_ok(rays_o, perturb, return_mask, kwargs):
+        if self._fused_ok(rays_o, perturb, return_mask, kwargs, bg_color):
             from samnerf_amd.fused import FusedRenderer
             if self._fused is None or self._fused.net is not self:
                 self._fused = FusedRenderer(self)

@@ -44,6 +44,11 @@ class SamnerfModel(ctypes.Structure):
                 ("perturb_device", _int), ("perturb_seed", _u64), ("perturb_offset", _u64)]
 
 
+class SamnerfBackground(ctypes.Structure):
+    """samnerf_background (include/samnerf_hip.h): samnerf_set_background's argument."""
+    _fields_ = [("background", _int), ("bg_rgb", _vp), ("n_bg", _u32)]
+
+
 _SIGS = {
     "samnerf_diag_variants": ([], _int),
     "samnerf_version": ([], ctypes.c_char_p),
@@ -68,6 +73,7 @@ _SIGS = {
     "samnerf_linspace_host": ([_f32, _f32, _u32, ctypes.POINTER(_f32)], None),
     "samnerf_perturb_host": ([_u64, _u64, ctypes.POINTER(_u32), _u32, _u32, ctypes.POINTER(_f32)], _int),
     "samnerf_perturb_fill": ([_u64, _u64, _u32, ctypes.POINTER(_u32), _vp, _vp, _vp, _vp], _int),
+    "samnerf_set_background": ([ctypes.POINTER(SamnerfBackground)], _int),
     "samnerf_render_workspace_size": ([ctypes.POINTER(SamnerfModel), _u32], _sz),
     "samnerf_render_forward": ([ctypes.POINTER(SamnerfModel), _vp, _vp, _u32, _vp, _u32, _f32,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp], _int),

@@ -13,7 +13,7 @@ import dataclasses
 import numpy as np
 import torch
 
-from ._lib import SamnerfGrid, SamnerfModel, SamnerfRgbGrads, SamnerfTaps, check, lib
+from ._lib import SamnerfBackground, SamnerfGrid, SamnerfModel, SamnerfRgbGrads, SamnerfTaps, check, lib
 from .ops import _ptr, _stream
 
 ROW = 164          # head-input row: f_sam 128 | f_image 31 | image 3 | depth 1 | pad
@@ -91,6 +91,77 @@ def set_perturb(m, pert):
     m.perturb_offset = pert.offset if seeded else 0
     for i in range(3):
         m.perturb[i] = None if (pert is None or seeded) else _param(pert[i], f"perturb[{i}]")
+
+
+def bg_layout(bg_color, N):
+    """How a reference-style bg_color reaches the kernels for a call over N
+    rays, as a pure function of its type and shape: (scalar, n_bg).  n_bg = 0:
+    the scalar background argument (None -> 1, a Python number, a 1-element
+    tensor); n_bg = 1: one RGB colour for every ray ([3] or [1,3], the GUI's
+    colour; scalar is None); n_bg = N: a colour per ray (anything else that
+    broadcasts against [N,3], e.g. [N,3] or [N,1] -- training under
+    --background random).  Any other shape is a ValueError."""
+    if bg_color is None:
+        return 1.0, 0
+    if not torch.is_tensor(bg_color):
+        return float(bg_color), 0
+    if bg_color.numel() == 1:
+        return float(bg_color), 0
+    shape = tuple(bg_color.shape)
+    if shape in ((3,), (1, 3)):
+        return None, 1
+    try:
+        ok = torch.broadcast_shapes(shape, (N, 3)) == (N, 3)
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"bg_color of shape {shape} does not broadcast against [{N}, 3]")
+    return None, N
+
+
+def background_rows(bg_color, N, device):
+    """(scalar, rows): bg_layout's scalar (1.0 where the colours are rows) and
+    the contiguous float32 [n_bg,3] tensor on `device` samnerf_background.bg_rgb
+    points at, or None.  A colour on another device is moved (the GUI builds
+    its colour on the CPU, as Trainer.test_step moves it); no gradient."""
+    scalar, n_bg = bg_layout(bg_color, N)
+    if n_bg == 0:
+        return scalar, None
+    t = bg_color.detach().to(device=device, dtype=torch.float32)
+    t = t.reshape(1, 3) if n_bg == 1 else t.broadcast_to((N, 3))
+    return 1.0, t.contiguous()
+
+
+def background_mode(net):
+    """samnerf_background.background of a network's --background option: 0 for
+    'last_sample', 1 (transparent) for 'white' and 'random', which differ only
+    in the colour the caller passes: both skip the last sample's +inf
+    (renderer.py:314)."""
+    return 0 if getattr(net.opt, "background", "last_sample") == "last_sample" else 1
+
+
+def set_background(net, rows):
+    """samnerf_set_background for the next calls of this thread: the network's
+    compositing mode and the background colours of one call (background_rows'
+    tensor, kept alive by the caller; None: the scalar argument).
+    set_background(None, None) restores the library's defaults -- callers do
+    that in a finally, as for the perturb pointers."""
+    # (an older build loaded through SAMNERF_LIB for an A/B has no setter: it
+    # knows the defaults only)
+    setter = getattr(lib(), "samnerf_set_background", None)
+    mode = 0 if net is None else background_mode(net)
+    if setter is None:
+        if mode != 0 or rows is not None:
+            raise RuntimeError("this build of the library has no background modes or colours")
+        return
+    if net is None:
+        check(setter(None), "set_background")
+        return
+    b = SamnerfBackground()
+    b.background = mode
+    b.bg_rgb = None if rows is None else ctypes.c_void_p(rows.data_ptr())
+    b.n_bg = 0 if rows is None else int(rows.shape[0])
+    check(setter(ctypes.byref(b)), "set_background")
 
 
 def _steps3(num_steps):
@@ -342,6 +413,10 @@ class FusedRenderer:
         columns 0-2 image, 3 depth, 4 weights_sum, 5-260 samvit
         (samnerf_render_forward_tile; the all-gather record of a sharded view)
         -- and returned as views of it.
+        bg_color: None (1), a number, a 1-element tensor, one RGB colour ([3]
+        or [1,3]) or anything that broadcasts against [N,3] (a colour per
+        ray; not with out_tile) -- bg_layout; a tensor on another device is
+        moved.  The compositing mode follows net.opt.background.
         perturb: False (default), True (draw the perturbed sample positions
         with torch's generator, perturbed_positions -- the reference's
         perturb=True), a (bins0, u1, u2) tuple of them [N, 129], [N, 65],
@@ -383,14 +458,10 @@ class FusedRenderer:
             pack_key = (ws.data_ptr(), self._pack_signature(m))
             have = self._packed.get((dev, _stream_key(dev)))
             m.reuse_packed = int(have is not None and have[0] == pack_key and (have[1] or not head))
-        if bg_color is None:
-            bg = 1.0
-        elif torch.is_tensor(bg_color):
-            if bg_color.numel() != 1:
-                raise NotImplementedError("fused render: per-ray background colours")
-            bg = float(bg_color)
-        else:
-            bg = float(bg_color)
+        bg, bg_rows = background_rows(bg_color, N, dev)
+        if out_tile is not None and bg_rows is not None and bg_rows.shape[0] != 1:
+            raise NotImplementedError("fused render: a per-ray background with out_tile (a sharded view "
+                                      "takes a scalar or one colour)")
         if out_tile is not None:
             need_c = 261 if (m.with_sam and feats) else 5
             if (out_tile.dim() != 2 or out_tile.shape[0] != N or out_tile.shape[1] < need_c
@@ -433,6 +504,7 @@ class FusedRenderer:
                              rows_tap["rows2"].data_ptr(), rows_tap["srows"].data_ptr())
             check(lib().samnerf_set_taps(ctypes.byref(st), N), "set_taps")
         try:
+            set_background(self.net, bg_rows)
             if out_tile is not None:
                 check(lib().samnerf_render_forward_tile(
                     ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, bg, _ptr(out_tile),
@@ -457,6 +529,7 @@ class FusedRenderer:
             if taps:
                 lib().samnerf_set_taps(None, 0)
             set_perturb(m, None)
+            set_background(None, None)
             m.reuse_packed = 0
         out = {"image": image, "depth": depth, "weights_sum": wsum}
         if mask and mask_logits:
@@ -724,8 +797,10 @@ class _FusedRGBTrain(torch.autograd.Function):
         weights = torch.empty(N, int(m.num_steps[2]), device=dev)
         losses = torch.zeros(2, device=dev)
         n_cnf = 0 if cnf is None else cnf.shape[0]
+        bg, bg_rows = bg                     # background_rows: the scalar, the [n_bg,3] colours or None
         try:
             set_perturb(m, pert)
+            set_background(renderer.net, bg_rows)
             check(lib().samnerf_rgb_train_forward(
                 ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, float(bg), int(with_prop),
                 _ptr(image), _ptr(depth), _ptr(wsum), _ptr(weights), _ptr(losses), _ptr(ws), need,
@@ -733,7 +808,8 @@ class _FusedRGBTrain(torch.autograd.Function):
                 "rgb_train_forward")
         finally:
             set_perturb(m, None)
-        ctx.state = (renderer, m, rays_o, rays_d, bg, pert, with_prop, ws, need, list(renderer._keep))
+            set_background(None, None)
+        ctx.state = (renderer, m, rays_o, rays_d, (bg, bg_rows), pert, with_prop, ws, need, list(renderer._keep))
         ctx.shapes = [p.shape for p in params]
         # outputs the loss does not use arrive as None (no zero tensors to
         # read): only results['weights'] usually is
@@ -742,7 +818,7 @@ class _FusedRGBTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_img, g_depth, g_wsum, g_prop, g_dist, g_weights):
-        renderer, m, rays_o, rays_d, bg, pert, with_prop, ws, need, _ = ctx.state
+        renderer, m, rays_o, rays_d, (bg, bg_rows), pert, with_prop, ws, need, _ = ctx.state
         dev = rays_o.device
         N = rays_o.shape[0]
         # a loss without proposal_loss leaves the proposal networks' .grad None,
@@ -771,12 +847,14 @@ class _FusedRGBTrain(torch.autograd.Function):
                     g.prop_mlp[q][i] = grads[9 + 2 * q + i].data_ptr()
         try:
             set_perturb(m, pert)             # the forward's arrays, or its (seed, offset)
+            set_background(renderer.net, bg_rows)   # and the forward's mode and colours
             check(lib().samnerf_rgb_train_backward(
                 ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, float(bg), int(with_prop), _ptr(g_img),
                 _ptr(g_ws), _ptr(g_dp), _ptr(g_w), _ptr(g_loss),
                 ctypes.byref(g), _ptr(ws), need, _stream(g_img)), "rgb_train_backward")
         finally:
             set_perturb(m, None)
+            set_background(None, None)
         if not with_prop:
             grads = grads[:7] + [None] * (len(grads) - 7)
         return (None,) * 7 + tuple(grads)
@@ -789,14 +867,14 @@ def render_rgb_train(renderer, rays_o, rays_d, cam_near_far=None, bg_color=None,
     when lambda_proposal > 0 and update_proposal -- proposal_loss, when
     lambda_distort > 0 distort_loss, all differentiable on the HIP training
     kernels (rgb_train.hip).  perturb as FusedRenderer.render's (False, True,
-    the three arrays, or a PhiloxPerturb)."""
+    the three arrays, or a PhiloxPerturb), bg_color too (a scalar, one colour
+    or a colour per ray; no gradient flows to it)."""
     net = renderer.net
     opt = net.opt
     rays_o = rays_o.contiguous().float()
     rays_d = rays_d.contiguous().float()
     N = rays_o.shape[0]
-    bg = 1.0 if bg_color is None else (float(bg_color) if not torch.is_tensor(bg_color) else
-                                        float(bg_color.reshape(())))
+    bg = background_rows(bg_color, N, rays_o.device)
     m = renderer.model()
     pert = None
     if isinstance(perturb, PhiloxPerturb):

@@ -65,24 +65,26 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     import ctypes
 
     from ._lib import SamnerfRgbGrads, SamnerfRgbTrainOpts, check, lib
-    from .fused import FusedRenderer, PhiloxPerturb, perturbed_positions, rgb_train_params, set_perturb
+    from .fused import (FusedRenderer, PhiloxPerturb, background_rows, perturbed_positions, rgb_train_params,
+                        set_background, set_perturb)
     from .ops import _ptr, _stream
 
     opt = model.opt
     if bg_color is None:
         bg_color = 1
+    if torch.is_tensor(bg_color) and bg_color.device != gt_rgb.device:
+        bg_color = bg_color.to(gt_rgb.device)
     if gt_rgb.shape[-1] == 4:
         gt_rgb = gt_rgb[..., :3] * gt_rgb[..., 3:] + bg_color * (1 - gt_rgb[..., 3:])
-    if torch.is_tensor(bg_color):
-        if bg_color.numel() != 1:
-            raise NotImplementedError("fused RGB step: per-ray background colours")
-        bg_color = float(bg_color)
     update_proposal = update_proposal_now(global_step, opt.with_sam)
     rays_o = rays_o.contiguous().float()
     rays_d = rays_d.contiguous().float()
     gt = gt_rgb.reshape(-1, 3).contiguous().float()
     N = rays_o.shape[0]
     dev = rays_o.device
+    # a scalar, one colour or a colour per ray (samnerf_background.bg_rgb overrides
+    # the options' scalar); no gradient flows to it
+    bg_scalar, bg_rows = background_rows(bg_color, N, dev)
     fr = getattr(model, "_fused_train", None)
     if fr is None or fr.net is not model:
         fr = model._fused_train = FusedRenderer(model, head_mode=1)
@@ -102,7 +104,7 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     o.lambda_distort = float(getattr(opt, "lambda_distort", 0.0))
     o.lambda_entropy = float(getattr(opt, "lambda_entropy", 0.0))
     o.update_proposal = int(bool(update_proposal))
-    o.bg_color = float(bg_color)
+    o.bg_color = float(bg_scalar)
     with_prop = bool(update_proposal) and o.lambda_proposal > 0
     every = rgb_train_params(model, True)
     main, prop = every[:7], every[7:]
@@ -139,12 +141,14 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     wsum = torch.empty(N, device=dev)
     loss = torch.empty(5, device=dev)
     try:
+        set_background(model, bg_rows)
         check(lib().samnerf_rgb_train_step(
             ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, _ptr(gt),
             ctypes.byref(o), _ptr(image), _ptr(depth), _ptr(wsum), _ptr(loss), ctypes.byref(g),
             _ptr(ws), need, _stream(rays_o)), "rgb_train_step")
     finally:
         set_perturb(m, None)
+        set_background(None, None)
     for p, t in zip(trained, scratch):
         if p.grad is None:
             p.grad = t
