@@ -627,6 +627,66 @@ int samnerf_last_forms(uint32_t* out, uint32_t n);
  * d(memtime) / d(memrealtime) x 100 MHz.  Costs one ~5-us launch. */
 int samnerf_clock_stamp(uint64_t* out, samnerf_stream_t stream);
 
+/* ------------------------------------------------------------- mask loss --
+ * The loss of Trainer.train_step's --with_mask branch (nerf/utils.py:959-1067)
+ * and its gradient to the logits, in fp32 and in fixed-order sums (no float
+ * atomics; the same inputs give the same bits whatever ran before).
+ * logits [N,K], K = n_inst + redundant_instance in [2, 32]; the first n rays are
+ * the global rays (opt.num_rays), the rest L local patches of Q pixels.
+ *   NLL (always): mean over the global rays of -log clamp(softmax(z))[label],
+ *     0 if no ray of all N is labelled (label != -1); with incoherent_weight
+ *     u < 1 times the mean over all N rays of 1 - m + u * m (the reference's
+ *     [n,1] x [N] broadcast, utils.py:979).
+ *   error map (error_map != NULL): map[c_i] <- 0.1 map[c_i] + 0.9 exp(-a cos(p_i,
+ *     onehot(label_i)) - epsilon) for the global rays, every old value read
+ *     before any is written, the last ray in ray order winning a shared cell
+ *     (utils.py:981-1017).  error_cells [n] are flat cells of the map.
+ *   label regularisation (label_reg_weight > 0, utils.py:843-870): over all N
+ *     rays as P x P patches of the softmax and depth; P >= 2, N % (P * P) == 0.
+ *   RGB similarity (rgb_weight > 0, utils.py:761-841 under :1034-1059): per
+ *     local patch, S samples sample_index [L,S] against its Q pixels of image
+ *     [N,3]; redundant != 0: the binary-cross-entropy form; use_pred_logistics:
+ *     the sample's softmax instead of its arg-max one-hot.  N == n + L * Q,
+ *     Q * K <= 8192, Q <= 1024, S <= min(Q, 256).
+ * The caller applies the reference's step condition (utils.py:1033) by leaving
+ * rgb_weight 0.  A label outside [0,K) among the global rays, a sample outside
+ * [0,Q) or a cell outside [0,map_cells) is never used as an index: that ray or
+ * sample contributes nothing and is counted in loss_terms[4]. */
+typedef struct {
+    uint32_t N, K, n;
+    uint32_t L, Q, S;              /* RGB similarity; 0 when off */
+    uint32_t P;                    /* label regularisation patch side */
+    int32_t redundant;
+    int32_t use_pred_logistics;
+    float incoherent_weight;       /* u; >= 1: no re-weighting */
+    float label_reg_weight;
+    float rgb_weight;
+    float rgb_threshold;
+    float rgb_exp_weight;          /* a (also the error map's) */
+    double epsilon;                /* the clamp is [epsilon, 1 - epsilon], each rounded to float */
+    uint64_t map_cells;
+    const int64_t* labels;         /* [N], -1 = unlabelled */
+    const float* incoherent;       /* [N]; read when incoherent_weight < 1 */
+    float* error_map;              /* [map_cells], updated in place; NULL = off */
+    const int64_t* error_cells;    /* [n] */
+    const float* depth;            /* [N]; read when label_reg_weight > 0 */
+    const float* image;            /* [N,3]; read when rgb_weight > 0 */
+    const int64_t* sample_index;   /* [L,S]; read when rgb_weight > 0 */
+} samnerf_mask_loss_args;
+
+/* Bytes of workspace samnerf_mask_loss needs for these sizes (0 for invalid ones). */
+size_t samnerf_mask_loss_workspace_size(const samnerf_mask_loss_args* args);
+
+/* loss_terms [5]: NLL, label regularisation, RGB similarity (each unweighted),
+ * their weighted total (utils.py:1026-1059) and the count of invalid inputs;
+ * grad_logits [N,K] = d total / d logits (written, not accumulated); pred_ids
+ * [N] int64 = argmax of the softmax, the first index winning ties.
+ * SAMNERF_EINVAL: a null pointer, K outside [2, 32] or inconsistent sizes;
+ * SAMNERF_EWORKSPACE: ws NULL or ws_bytes too small. */
+int samnerf_mask_loss(const samnerf_mask_loss_args* args, const float* logits, float* loss_terms,
+                      float* grad_logits, int64_t* pred_ids, void* ws, size_t ws_bytes,
+                      samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

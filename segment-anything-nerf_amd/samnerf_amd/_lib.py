@@ -49,6 +49,16 @@ class SamnerfBackground(ctypes.Structure):
     _fields_ = [("background", _int), ("bg_rgb", _vp), ("n_bg", _u32)]
 
 
+class SamnerfMaskLossArgs(ctypes.Structure):
+    """samnerf_mask_loss_args (include/samnerf_hip.h)."""
+    _fields_ = [("N", _u32), ("K", _u32), ("n", _u32), ("L", _u32), ("Q", _u32), ("S", _u32), ("P", _u32),
+                ("redundant", ctypes.c_int32), ("use_pred_logistics", ctypes.c_int32),
+                ("incoherent_weight", _f32), ("label_reg_weight", _f32), ("rgb_weight", _f32),
+                ("rgb_threshold", _f32), ("rgb_exp_weight", _f32), ("epsilon", _f64), ("map_cells", _u64),
+                ("labels", _vp), ("incoherent", _vp), ("error_map", _vp), ("error_cells", _vp),
+                ("depth", _vp), ("image", _vp), ("sample_index", _vp)]
+
+
 _SIGS = {
     "samnerf_diag_variants": ([], _int),
     "samnerf_version": ([], ctypes.c_char_p),
@@ -112,6 +122,8 @@ _SIGS = {
     "samnerf_mask_train_forward": ([ctypes.POINTER(SamnerfModel), _u32, _vp, _vp, _sz, _vp, _sz, _vp], _int),
     "samnerf_mask_train_backward": ([ctypes.POINTER(SamnerfModel), _u32, _vp, ctypes.POINTER(_vp), _vp, _vp,
                                      _sz, _vp, _sz, _vp], _int),
+    "samnerf_mask_loss_workspace_size": ([ctypes.POINTER(SamnerfMaskLossArgs)], _sz),
+    "samnerf_mask_loss": ([ctypes.POINTER(SamnerfMaskLossArgs), _vp, _vp, _vp, _vp, _vp, _sz, _vp], _int),
 }
 
 

@@ -201,3 +201,52 @@ def mask_train_step(model, rays_o, rays_d, gt_mask, num_rays=None, cam_near_far=
     else:
         loss = torch.zeros((), dtype=pred.dtype, device=pred.device)
     return pred.argmax(dim=-1), loss.mean()
+
+
+def mask_train_step_full(model, data, global_step, error_map=None, check_inputs=True):
+    """The whole --with_mask branch of Trainer.train_step (nerf/utils.py:941-1070)
+    with the reference's `data` keys: rays_o, rays_d, masks [B, N] and, where
+    the options ask for them, incoherent_masks (the re-weighting; the sampling
+    weights of the RGB-similarity draw without --error_map), error_maps (those
+    weights with --error_map), inds_coarse + index (the error map's cells) and
+    cam_near_far.  error_map: the Trainer's [images, M * M] tensor
+    (self.error_map), updated in place, or None.  The first opt.num_rays rays
+    are the global rays, the rest opt.num_local_sample patches of
+    opt.local_sample_patch_size ** 2 pixels (--mixed_sampling).
+
+    The render is mask_train_step's; the loss is samnerf_amd.mask_loss: on a
+    CUDA model one C call (csrc/mask_loss.hip) for the loss and its gradient
+    to the logits, on a CPU model the reference's torch ops.  The only host
+    work per step is the RGB-similarity draw (torch.multinomial, as
+    utils.py:779-790) and, under check_inputs, one read-back of the count of
+    invalid inputs.  Returns (pred_ids, gt_mask, loss) like the reference."""
+    from .mask_loss import draw_similarity_samples, mask_loss, rgb_similarity_active
+    opt = model.opt
+    rays_o, rays_d = data["rays_o"], data["rays_d"]
+    gt_mask = data["masks"].to(torch.long)
+    cam_near_far = data["cam_near_far"] if "cam_near_far" in data else None
+    outputs = model.render(rays_o, rays_d, staged=False, bg_color=1, perturb=False,
+                           cam_near_far=cam_near_far, update_proposal=False, return_feats=0,
+                           return_mask=1)
+    logits = outputs["instance_mask_logits"]
+    logits = logits.reshape(-1, logits.shape[-1])
+    N = logits.shape[0]
+    n = min(int(opt.num_rays), N)
+    kw = {}
+    if getattr(opt, "incoherent_uncertainty_weight", 1) < 1:
+        kw["incoherent"] = data["incoherent_masks"].reshape(-1)
+    if error_map is not None:
+        index = torch.as_tensor(data["index"], device=logits.device).reshape(-1, 1)
+        cells = index * error_map.shape[-1] + data["inds_coarse"].reshape(index.shape[0], -1)
+        kw["error_map"], kw["error_cells"] = error_map, cells.reshape(-1)[:n]
+    if getattr(opt, "label_regularization_weight", 0) > 0:
+        kw["depth"] = outputs["depth"].detach().reshape(-1)
+    if rgb_similarity_active(opt, global_step) and getattr(opt, "mixed_sampling", False):
+        L, Q = int(opt.num_local_sample), int(opt.local_sample_patch_size) ** 2
+        src = data["error_maps"] if getattr(opt, "error_map", False) else data["incoherent_masks"]
+        kw["image"] = outputs["image"].detach().reshape(-1, 3)
+        kw["sample_index"] = draw_similarity_samples(src.reshape(-1)[n:].view(L, Q),
+                                                     int(opt.rgb_similarity_num_sample))
+    loss, _, pred_ids = mask_loss(logits, gt_mask.reshape(-1), n, opt, global_step=global_step,
+                                  check_inputs=check_inputs, **kw)
+    return pred_ids, gt_mask, loss
