@@ -687,6 +687,162 @@ int samnerf_mask_loss(const samnerf_mask_loss_args* args, const float* logits, f
                       float* grad_logits, int64_t* pred_ids, void* ws, size_t ws_bytes,
                       samnerf_stream_t stream);
 
+/* --------------------------------------------------------- batch sampler --
+ * A training step's input: the N > 0 branches of the reference's get_rays
+ * (nerf/utils.py:174-242) choose the pixels, and its collate
+ * (nerf/colmap_provider.py:1084-1175) gathers the ground truth at them.  All
+ * pointers are device pointers unless named _host.
+ *
+ * The tables of a dataset; any but poses / intrinsics may be NULL. */
+typedef struct {
+    const float* poses;            /* [n_img,4,4] cam2world */
+    const float* intrinsics;       /* [n_intr,4] fx, fy, cx, cy; n_intr = n_img or 1 */
+    uint32_t n_img, n_intr;
+    uint32_t H, W;                 /* of images and masks; H also scales the map reads */
+    const void* images;            /* [n_img,H,W,C] uint8, or float32 when images_float */
+    uint32_t C;                    /* 1..4 */
+    int32_t images_float;
+    const int64_t* masks;          /* [n_img,H,W] instance labels */
+    const void* incoherent_masks;  /* [n_img, incoherent_size^2], 1-byte (bool / uint8) or float32 cells */
+    uint32_t incoherent_bytes;     /* 1 or 4 */
+    uint32_t incoherent_size;
+    const float* error_map;        /* [n_img, error_size^2] */
+    uint32_t error_size;
+    const float* cam_near_far;     /* [n_img,2] */
+} samnerf_batch_source;
+
+/* What the gather writes for n rays; a NULL output, or one whose table is
+ * NULL, is not written. */
+typedef struct {
+    float* rays_o;                 /* [n,3] */
+    float* rays_d;                 /* [n,3] */
+    int64_t* i;                    /* [n] column */
+    int64_t* j;                    /* [n] row */
+    int64_t* inds_coarse;          /* [n] */
+    float* images;                 /* [n,C] = pixel / 255 */
+    int64_t* masks;                /* [n] */
+    void* incoherent_masks;        /* [n], the table's cell type */
+    float* error_maps;             /* [n] */
+    float* cam_near_far;           /* [n,2] */
+} samnerf_batch_out;
+
+/* k_batch_gather, one launch: ray t is pixel pixels[t] = row * W + col of image
+ * index[n_index == 1 ? 0 : t] (n_index = 1 or n), in an H x W ray image (the
+ * tables' size, or the fixed-fov size of colmap_provider.py:1009-1015, which
+ * must not exceed it).
+ *   rays_o, rays_d  utils.py:247-259 in its op order: ((col + 0.5) - cx) / fx,
+ *                   -((row + 0.5) - cy) / fy, -1, times R^T (a product and two
+ *                   fmas per component), true divisions; pose and intrinsics
+ *                   read per ray
+ *   inds_coarse     utils.py:269-275 with incoherent_mask_size = coarse_size:
+ *                   (long)(row * (float)(coarse_size / H)) * coarse_size +
+ *                   (long)(col * (float)(coarse_size / W)), products in
+ *                   float32; coarse_size = 0: not written
+ *   images          colmap_provider.py:1086, (float)pixel / 255, a true division
+ *   incoherent_masks, error_maps   colmap_provider.py:1116-1158: the cell
+ *                   (long)(row * s) * S + (long)(col * s), s = (float)(S / H)
+ *                   for rows AND columns as the reference has it; a cell past
+ *                   the map (W > H) is not read and its output not written
+ * A ray whose image or pixel is out of range writes nothing.
+ * SAMNERF_EINVAL: a null pointer, n_index not 1 or n, H x W beyond the tables. */
+int samnerf_batch_gather(const samnerf_batch_source* src, const int64_t* index, uint32_t n_index,
+                         const int64_t* pixels, uint32_t n, uint32_t H, uint32_t W, uint32_t coarse_size,
+                         const samnerf_batch_out* out, samnerf_stream_t stream);
+
+/* The pixel choice.  Every mode takes its raw draws either from arrays (seeded
+ * = 0: the reference's torch stream, or samnerf_batch_draw_fill's replay) or
+ * from Philox4x32-10 under (seed, offset) (seeded = 1).  Statistically the
+ * reference's sampling, NOT torch's generator stream.  The seeded contract,
+ * exact to the bit (generator and key as samnerf_model.perturb_device's):
+ *   counters   the perturb stages use c0 >> 16 = 0, 1, 2; these use 3..7, so a
+ *              (seed, offset) shared with a render reuses none of its words.
+ *              Item t (a ray, a patch or a map row, below): c0 = 3 << 16, c1 =
+ *              t; cell c of map row b: c0 = (4 << 16) + (c >> 2), c1 = b, the
+ *              cell's word is output word c & 3 (c < 2^20).  c2, c3 = offset.
+ *   integer    in [0, R): (uint64(word) * R) >> 32; its bias is at most R / 2^32
+ *   item t     word 0 -> first integer, word 1 -> second integer, words 2, 3 ->
+ *              uniforms r = (word >> 8) * 2^-24 in [0, 1) (torch.rand's range)
+ *   key        of a cell of weight w: w / e, e = -log(u), u = ((word >> 8) +
+ *              0.5) * 2^-24, never 0 or 1 (for word >> 8 >= 2^23, where fp32 no
+ *              longer holds u, e = -log1p(-(1 - u)) with 1 - u exact); a
+ *              weight that is not positive and finite has key 0, one that is a
+ *              key of at least the smallest subnormal.  fp32, the device's logf
+ *              and log1pf: keys exist only on the device (the fill below).
+ * Modes (n = rays for R and E, patches for P, map rows for C):
+ *   SAMNERF_BATCH_UNIFORM (R)  utils.py:234-236 with colmap_provider.py:975 /
+ *       :978.  Item = ray: index = integer(n_img), pixel = integer(H * W).
+ *       Arrays: int0 = images, int1 = pixels [n].
+ *   SAMNERF_BATCH_PATCHES (P)  utils.py:196-219.  Item = patch: corner row =
+ *       integer(H - p), col = integer(W - p); pixels [n * p * p], patch after
+ *       patch, pixel k of a patch at (row + k / p, col + k % p).  Arrays: int0 =
+ *       corner rows, int1 = corner cols [n].
+ *   SAMNERF_BATCH_CENTRED (C)  utils.py:180-194, :206-219; the local draws of
+ *       mixed sampling, colmap_provider.py:1049-1070.  Map row b is the M x M
+ *       weights of image rows[b]; rows = NULL (seeded only): item = map row,
+ *       image = integer(n_img).  The centre is the cell of largest key, the
+ *       lower cell winning a tie: for one draw, exactly proportional to the
+ *       weights.  corner = (long)clamp(c / M * (float)(H / M) - p / 2, 0, H - p
+ *       - 1) in float32 (likewise the column); pixels and index [n * p * p],
+ *       cells [n] (the centres, may be NULL).  Arrays: keys [n, M * M].  M <=
+ *       1024, 1 <= p < min(H, W).
+ *   SAMNERF_BATCH_ERROR (E)  utils.py:222-233.  The n cells of largest key of
+ *       the map of image rows[0] -- weighted sampling without replacement, the
+ *       exponential-key scheme torch.multinomial uses -- ties to the lower
+ *       cell, written in ascending cell order to cells [n]; pixel of slot k =
+ *       min((long)(cell_row * sx + r0 * sx), H - 1) * W + likewise the column,
+ *       sx = (float)(H / M), item = slot k.  M = 128 only (the reference
+ *       divides by a literal 128), n <= 16384.  Arrays: keys [M * M] (16-byte
+ *       aligned), u0, u1 [n].
+ * Precondition of C and E: the row holds at least n (C: one) positive finite
+ * weights.  Otherwise cells of weight 0 are chosen, lowest first; nothing is
+ * read or written out of bounds. */
+enum {
+    SAMNERF_BATCH_UNIFORM = 0,
+    SAMNERF_BATCH_PATCHES = 1,
+    SAMNERF_BATCH_CENTRED = 2,
+    SAMNERF_BATCH_ERROR = 3
+};
+
+typedef struct {
+    int32_t mode;
+    int32_t seeded;
+    uint64_t seed, offset;
+    uint32_t n_img, H, W;
+    uint32_t n;
+    uint32_t patch;                /* P, C */
+    uint32_t M;                    /* C, E */
+    const void* weights;           /* C, E seeded: [n_img, M * M] */
+    uint32_t weight_bytes;         /* 4: float32; 1: bool / uint8 */
+    const int64_t* rows;           /* C: [n] or NULL; E: [1] */
+    const int64_t* int0;           /* the array form's draws, per mode above */
+    const int64_t* int1;
+    const float* keys;
+    const float* u0;
+    const float* u1;
+    int64_t* index;                /* R: [n]; C: [n * p * p] or NULL */
+    int64_t* pixels;
+    int64_t* cells;                /* C: [n] or NULL; E: [n] */
+} samnerf_batch_draw_args;
+
+int samnerf_batch_draw(const samnerf_batch_draw_args* args, samnerf_stream_t stream);
+
+/* The raw draws of a (seed, offset) as arrays, to log or replay a step:
+ * samnerf_batch_draw with seeded = 0 fed these equals seeded = 1 bit for bit.
+ * int0, int1 [items]: the two integers of every item under range0, range1; u0,
+ * u1 [items]: its uniforms; keys [B, cells]: the keys of map rows 0..B-1 over
+ * weights [n_img, cells], row b being image rows[b] or, rows = NULL, the first
+ * integer of item b under n_img.  Any output may be NULL. */
+int samnerf_batch_draw_fill(uint64_t seed, uint64_t offset, uint32_t items, uint32_t range0, uint32_t range1,
+                            int64_t* int0, int64_t* int1, float* u0, float* u1, const void* weights,
+                            uint32_t weight_bytes, uint32_t n_img, const int64_t* rows, uint32_t B,
+                            uint32_t cells, float* keys, samnerf_stream_t stream);
+
+/* Host only, no GPU needed: the integers (ints_host[2], under range0 and
+ * range1) and uniforms (uniforms_host[2]) of item `item`.  They use no libm, so
+ * host and device agree exactly. */
+int samnerf_batch_draw_host(uint64_t seed, uint64_t offset, uint32_t item, uint32_t range0, uint32_t range1,
+                            int64_t* ints_host, float* uniforms_host);
+
 #ifdef __cplusplus
 }
 #endif

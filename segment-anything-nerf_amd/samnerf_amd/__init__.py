@@ -3,5 +3,6 @@
   ops       tensor-level wrappers of the C ABI (encoders + step kernels)
   fused     FusedRenderer: NeRFRenderer.run as five fused kernel launches
   dist      ray sharding over ranks + RCCL all-gather of output tiles
+  batch     TrainBatchSampler: a training step's ray choice and collate gathers
 """
 from ._lib import EXPORTED, LIB_PATH, SamnerfUnavailable, lib  # noqa: F401

@@ -59,6 +59,28 @@ class SamnerfMaskLossArgs(ctypes.Structure):
                 ("depth", _vp), ("image", _vp), ("sample_index", _vp)]
 
 
+class SamnerfBatchSource(ctypes.Structure):
+    """samnerf_batch_source (include/samnerf_hip.h)."""
+    _fields_ = [("poses", _vp), ("intrinsics", _vp), ("n_img", _u32), ("n_intr", _u32), ("H", _u32), ("W", _u32),
+                ("images", _vp), ("C", _u32), ("images_float", ctypes.c_int32), ("masks", _vp),
+                ("incoherent_masks", _vp), ("incoherent_bytes", _u32), ("incoherent_size", _u32),
+                ("error_map", _vp), ("error_size", _u32), ("cam_near_far", _vp)]
+
+
+class SamnerfBatchOut(ctypes.Structure):
+    """samnerf_batch_out (include/samnerf_hip.h)."""
+    _fields_ = [(k, _vp) for k in ("rays_o", "rays_d", "i", "j", "inds_coarse", "images", "masks",
+                                   "incoherent_masks", "error_maps", "cam_near_far")]
+
+
+class SamnerfBatchDrawArgs(ctypes.Structure):
+    """samnerf_batch_draw_args (include/samnerf_hip.h)."""
+    _fields_ = [("mode", ctypes.c_int32), ("seeded", ctypes.c_int32), ("seed", _u64), ("offset", _u64),
+                ("n_img", _u32), ("H", _u32), ("W", _u32), ("n", _u32), ("patch", _u32), ("M", _u32),
+                ("weights", _vp), ("weight_bytes", _u32), ("rows", _vp), ("int0", _vp), ("int1", _vp),
+                ("keys", _vp), ("u0", _vp), ("u1", _vp), ("index", _vp), ("pixels", _vp), ("cells", _vp)]
+
+
 _SIGS = {
     "samnerf_diag_variants": ([], _int),
     "samnerf_version": ([], ctypes.c_char_p),
@@ -124,6 +146,13 @@ _SIGS = {
                                      _sz, _vp, _sz, _vp], _int),
     "samnerf_mask_loss_workspace_size": ([ctypes.POINTER(SamnerfMaskLossArgs)], _sz),
     "samnerf_mask_loss": ([ctypes.POINTER(SamnerfMaskLossArgs), _vp, _vp, _vp, _vp, _vp, _sz, _vp], _int),
+    "samnerf_batch_gather": ([ctypes.POINTER(SamnerfBatchSource), _vp, _u32, _vp, _u32, _u32, _u32, _u32,
+                              ctypes.POINTER(SamnerfBatchOut), _vp], _int),
+    "samnerf_batch_draw": ([ctypes.POINTER(SamnerfBatchDrawArgs), _vp], _int),
+    "samnerf_batch_draw_fill": ([_u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32,
+                                 _u32, _vp, _vp], _int),
+    "samnerf_batch_draw_host": ([_u64, _u64, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_int64),
+                                 ctypes.POINTER(_f32)], _int),
 }
 
 
