@@ -843,6 +843,79 @@ int samnerf_batch_draw_fill(uint64_t seed, uint64_t offset, uint32_t items, uint
 int samnerf_batch_draw_host(uint64_t seed, uint64_t offset, uint32_t item, uint32_t range0, uint32_t range1,
                             int64_t* ints_host, float* uniforms_host);
 
+/* ----------------------------------------------------- frame presentation --
+ * From a render's outputs to the GUI's display buffer: what Trainer.test_step
+ * (nerf/utils.py:1263-1306, :1396-1399), Trainer.test_gui (:1698-1702) and
+ * NeRFGUI.prepare_buffer / test_step (nerf/gui.py:134-140, :171-177) do after
+ * the render, in fp32 with every product and sum rounded on its own, in the
+ * reference's op order.  No model: it works on any render's outputs.  In order:
+ *   1. logits [rH*rW, K] (K = n_inst + redundant_instance in [1, 32]; K = 0: no
+ *      mask view): n_inst > 1 the softmax over the K columns (max, expf(z - max),
+ *      the 32-lane tree sum, division: samnerf_mask_loss's), n_inst == 1 the
+ *      sigmoid; then the largest probability and its index, the first index
+ *      winning ties;
+ *   2. the colour.  render id = instance_id if 0 <= instance_id < n_inst, else -1.
+ *      HEATMAP: color_map[id] * p[id], or color_map[argmax] * max at id -1;
+ *      COMPOSITION: image * 0.7f + c * 0.3f with c = color_map[argmax], or c = image
+ *      where an id is set and argmax != id (image * 0.7f + image * 0.3f, which is
+ *      not image); MASK: color_map[argmax] at id -1, else color_map[id] where
+ *      argmax == id and 0 elsewhere.  K = 0: the rendered image;
+ *   3. sam_mask [rH*rW] bytes: frame * 0.7f + o * 0.3f with o = (1, 0, 0) where the
+ *      byte is set and o = frame elsewhere (overlay_mask blends every pixel);
+ *   4. points [n_points, 2] int32 (x, y), n_points <= 64: rows [y - 2, y + 2) and
+ *      columns [x - 2, x + 2) become (0, 1, 0) under Python's slice rules, as the
+ *      reference's indexing applies them: an end past the image is clipped, a
+ *      negative start wraps round to the far edge, so a click within 2 pixels of
+ *      the top or left edge selects an empty range and draws nothing;
+ *   5. nearest resize of frame and depth from rH x rW to H x W, ATen's rule:
+ *      src = min(floor(dst * (float)in / out), in - 1), the scale in fp32;
+ *   6. the buffer [H*W, 3].  SAMNERF_PRESENT_IMAGE: the frame.  _DEPTH:
+ *      (d - min) / (max - min + 1e-6f) on all three channels, min and max over
+ *      the resized depth; a NaN anywhere makes every value NaN (numpy's min /
+ *      max).  spp == 0: written; else (buffer * spp + new) / (spp + 1), spp as
+ *      fp32;
+ *   7. the side outputs, each optional: probs [rH*rW, K], ids [rH*rW] (the argmax),
+ *      depth_out [H*W] (the resized depth).
+ * The same inputs give the same bits: no float atomics, min and max are
+ * order-free. */
+enum { SAMNERF_PRESENT_HEATMAP = 0, SAMNERF_PRESENT_COMPOSITION = 1, SAMNERF_PRESENT_MASK = 2 };
+enum { SAMNERF_PRESENT_IMAGE = 0, SAMNERF_PRESENT_DEPTH = 1 };
+#define SAMNERF_PRESENT_MAX_POINTS 64
+
+typedef struct {
+    uint32_t rH, rW;               /* the render's size */
+    uint32_t H, W;                 /* the buffer's size */
+    uint32_t K, n_inst;            /* K = 0: no logits */
+    uint32_t n_colors;             /* rows of color_map; >= K */
+    uint32_t n_points;
+    uint32_t spp;                  /* frames already in the buffer */
+    int32_t mask_type;             /* SAMNERF_PRESENT_HEATMAP / _COMPOSITION / _MASK */
+    int32_t instance_id;           /* opt.render_mask_instance_id */
+    int32_t mode;                  /* SAMNERF_PRESENT_IMAGE / _DEPTH */
+    const float* image;            /* [rH*rW,3]; read at K = 0 and by COMPOSITION */
+    const float* depth;            /* [rH*rW]; read by _DEPTH and for depth_out */
+    const float* logits;           /* [rH*rW,K] */
+    const float* color_map;        /* [n_colors,3] */
+    const uint8_t* sam_mask;       /* [rH*rW], NULL = off */
+    const int32_t* points;         /* [n_points,2] */
+    float* buffer;                 /* [H*W,3]; read as well when spp > 0 */
+    float* probs;                  /* [rH*rW,K] or NULL */
+    int64_t* ids;                  /* [rH*rW] or NULL */
+    float* depth_out;              /* [H*W] or NULL */
+} samnerf_present_args;
+
+/* Bytes of workspace samnerf_present_frame needs (0 for invalid arguments, and
+ * for an image buffer at the render's own size, which takes one pass). */
+size_t samnerf_present_workspace_size(const samnerf_present_args* args);
+
+/* SAMNERF_EINVAL: a null pointer the mode needs, K outside [0, 32], n_inst
+ * outside [1, K], a color_map shorter than K rows (an argmax may reach past
+ * n_inst: redundant instances have colours too) or than the render id,
+ * n_points > 64, an unknown mask_type or mode, a size of 0 or of 2^31 values or
+ * more; SAMNERF_EWORKSPACE: workspace NULL or too small where one is needed. */
+int samnerf_present_frame(const samnerf_present_args* args, void* workspace, size_t workspace_bytes,
+                          samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

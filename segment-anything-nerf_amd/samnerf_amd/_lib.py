@@ -81,6 +81,15 @@ class SamnerfBatchDrawArgs(ctypes.Structure):
                 ("keys", _vp), ("u0", _vp), ("u1", _vp), ("index", _vp), ("pixels", _vp), ("cells", _vp)]
 
 
+class SamnerfPresentArgs(ctypes.Structure):
+    """samnerf_present_args (include/samnerf_hip.h)."""
+    _fields_ = [("rH", _u32), ("rW", _u32), ("H", _u32), ("W", _u32), ("K", _u32), ("n_inst", _u32),
+                ("n_colors", _u32), ("n_points", _u32), ("spp", _u32), ("mask_type", ctypes.c_int32),
+                ("instance_id", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("image", _vp), ("depth", _vp), ("logits", _vp), ("color_map", _vp), ("sam_mask", _vp),
+                ("points", _vp), ("buffer", _vp), ("probs", _vp), ("ids", _vp), ("depth_out", _vp)]
+
+
 _SIGS = {
     "samnerf_diag_variants": ([], _int),
     "samnerf_version": ([], ctypes.c_char_p),
@@ -153,6 +162,8 @@ _SIGS = {
                                  _u32, _vp, _vp], _int),
     "samnerf_batch_draw_host": ([_u64, _u64, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_int64),
                                  ctypes.POINTER(_f32)], _int),
+    "samnerf_present_workspace_size": ([ctypes.POINTER(SamnerfPresentArgs)], _sz),
+    "samnerf_present_frame": ([ctypes.POINTER(SamnerfPresentArgs), _vp, _sz, _vp], _int),
 }
 
 

@@ -76,11 +76,104 @@ def sam_predict(predictor, H, W, features, point_coords=None, mask_input=None, d
     return masks[0], original, low_res[0]
 
 
+class PromptMemory:
+    """The remembered 3D prompt points of Trainer.test_step (utils.py:1318-1384),
+    which make a click follow its object across views: a click is lifted to 3D
+    by the rendered depth; a new point is added, or takes out the remembered
+    points within `dist_thresh` of it; the remembered points are projected into
+    each view and kept where they are on screen and not occluded.  Plain torch
+    ops on a handful of points, on the tensors' device."""
+    dist_thresh = 0.01
+    depth_thresh = 0.05
+
+    def __init__(self):
+        self.point_3d = None
+
+    def update(self, point_coords, rays_o, rays_d, depth):
+        """utils.py:1318-1345.  point_coords [P, 2] (x, y) integer pixels of the
+        H x W view; rays_o, rays_d [H*W, 3]; depth [H, W]."""
+        H, W = depth.shape
+        pc = torch.as_tensor(np.asarray(point_coords), dtype=torch.long, device=depth.device)
+        rays_o, rays_d = rays_o.view(H, W, 3), rays_d.view(H, W, 3)
+        point_depth = depth[pc[:, 1], pc[:, 0]]
+        point_3d = rays_o[pc[:, 1], pc[:, 0]] + rays_d[pc[:, 1], pc[:, 0]] * point_depth.unsqueeze(-1)
+        if self.point_3d is None:
+            self.point_3d = point_3d
+            return
+        dist = (self.point_3d - point_3d).norm(dim=-1)
+        if dist.min() > self.dist_thresh:
+            self.point_3d = torch.cat([self.point_3d, point_3d], dim=0)
+        else:
+            keep_mask = dist > self.dist_thresh
+            self.point_3d = self.point_3d[keep_mask] if keep_mask.any() else None
+
+    def camera_points(self, pose):
+        """The remembered points in the camera frame of `pose` [4, 4]: [N, 4]."""
+        point_3d = torch.cat([self.point_3d, torch.ones_like(self.point_3d[:, :1])], axis=-1)
+        w2c = torch.inverse(torch.as_tensor(pose, dtype=point_3d.dtype, device=point_3d.device).view(4, 4))
+        return point_3d @ w2c.T
+
+    def project(self, pose, intrinsics, depth):
+        """utils.py:1349-1384: the remembered points as integer pixels (x, y) of
+        the view (pose [4, 4], intrinsics (fx, fy, cx, cy), its rendered depth
+        [H, W]), int64 numpy [M, 2], or None where none is on screen and
+        unoccluded."""
+        if self.point_3d is None:
+            return None
+        H, W = depth.shape
+        point_3d_cam = self.camera_points(pose)
+        fx, fy, cx, cy = [torch.as_tensor(intrinsics, dtype=point_3d_cam.dtype, device=point_3d_cam.device)
+                          .reshape(4)[i] for i in range(4)]
+        coords = torch.stack([
+            W - (fx * point_3d_cam[:, 0] / point_3d_cam[:, 2] + cx),
+            fy * point_3d_cam[:, 1] / point_3d_cam[:, 2] + cy,
+        ], dim=-1).long()
+        screen_mask = (coords[:, 0] >= 0) & (coords[:, 0] < W) & (coords[:, 1] >= 0) & (coords[:, 1] < H)
+        if not screen_mask.any():
+            return None
+        coords = coords[screen_mask]
+        point_depth = - point_3d_cam[screen_mask, 2]
+        observed_depth = depth[coords[:, 1], coords[:, 0]]
+        unoccluded_mask = (point_depth - observed_depth).abs() <= self.depth_thresh
+        if not unoccluded_mask.any():
+            return None
+        return coords[unoccluded_mask].detach().cpu().numpy()
+
+
 def render_and_predict(renderer, predictor, rays_o_lr, rays_d_lr, h, w, H, W, point_coords=None,
-                       **kw):
+                       memory=None, present=None, **kw):
     """The interactive loop of the GUI (nerf/gui.py:143-161, utils.py:1647-1712)
     on the fused path: render the h x w feature rays, hand the feature map to
-    the decoder without a host copy."""
+    the decoder without a host copy.
+
+    present: the H x W view to show the result on, a dict with 'image'
+    [H, W, 3] and 'depth' [H, W] and, for `memory` (a PromptMemory), 'rays_o',
+    'rays_d' [H*W, 3], 'pose' [4, 4], 'intrinsics' [4]; other keys go to
+    present.present_frame (mode, buffer, spp, ...).  With memory the click
+    updates the remembered points and the decoder is prompted with their
+    projection into this view (utils.py:1318-1394), or not run where none is
+    visible.  Returns (prediction or None, out, frame): the frame with the
+    decoder's mask and the click squares over it (utils.py:1396-1399).  Without
+    memory and present the result is (prediction, out), as before."""
     out = renderer.render(rays_o_lr, rays_d_lr)
     feats = out["samvit"].view(h, w, 256)
-    return sam_predict(predictor, H, W, feats, point_coords=point_coords, **kw), out
+    if memory is None and present is None:
+        return sam_predict(predictor, H, W, feats, point_coords=point_coords, **kw), out
+    from .present import present_frame
+    view = dict(present or {})
+    geometry = {k: view.pop(k, None) for k in ("rays_o", "rays_d", "pose", "intrinsics")}
+    image, depth = view.pop("image", None), view.pop("depth", None)
+    if memory is not None:
+        if depth is None or any(v is None for v in geometry.values()):
+            raise ValueError("render_and_predict: memory= needs present= with depth, rays_o, rays_d, pose, intrinsics")
+        if point_coords is not None:
+            memory.update(point_coords, geometry["rays_o"], geometry["rays_d"], depth)
+        point_coords = memory.project(geometry["pose"], geometry["intrinsics"], depth)
+    pred = None
+    if point_coords is not None:
+        pred = sam_predict(predictor, H, W, feats, point_coords=point_coords, **kw)
+    if present is None:
+        return pred, out, None
+    if pred is not None:
+        view.update(sam_mask=pred[0][0], points=pred[1])      # masks [N, H, W]: the first, as utils.py:1396
+    return pred, out, present_frame(image, depth, H, W, **view)
