@@ -916,6 +916,103 @@ size_t samnerf_present_workspace_size(const samnerf_present_args* args);
 int samnerf_present_frame(const samnerf_present_args* args, void* workspace, size_t workspace_bytes,
                           samnerf_stream_t stream);
 
+/* ------------------------------------------------------------- evaluation --
+ * What Trainer.eval_step (nerf/utils.py:1122-1241) and the meters of
+ * evaluate_one_epoch (PSNRMeter, SSIMMeter, MeanIoUMeter, utils.py:329-512,
+ * :1945-2000) compute from one evaluated view, as raw sums and counts in one
+ * stats record in device memory.  Nothing is copied to the host and nothing
+ * synchronises; the finished scalars (loss, PSNR, SSIM, mIoU) are the host's,
+ * in float64, from one copy of the records.  A record is a samnerf_eval_stats
+ * followed by three histograms of n_classes uint32 each (inter, npred,
+ * ntruth): SAMNERF_EVAL_STATS_BYTES(n_classes) bytes, 8-byte aligned.  Every
+ * call writes the whole record.  Each part is optional:
+ *   RGB (C = 3 or 4): truth [H*W,C]; at C = 4 the composite t = rgb * a +
+ *     bg_color * (1 - a), every product and sum rounded to fp32.  sq_sum = the
+ *     sum over H*W*3 of the fp32 (p - t)^2, n_elem = H*W*3, min and max of the
+ *     prediction and of t (a NaN is skipped).  pred_u8 / truth_u8 [H*W,3]:
+ *     (uint8)(v * 255.0f), truncated (v in [0, 1]); error_u8 [H*W]: the fp32
+ *     ((|t0 - p0| + |t1 - p1|) + |t2 - p2|) / 3 of those bytes, truncated;
+ *     truth_out [H*W,3]: t.
+ *   SSIM (ssim != 0, needs the RGB part and H, W >= 11): the 11-tap Gaussian
+ *     window of sigma 1.5, g[i] = exp(-((i - 5) / 1.5)^2 / 2) / sum as fp32 values
+ *     (a table: the double evaluation rounded once), applied as a row pass and
+ *     a column pass of fp32 FMAs, over
+ *     the (H - 10) * (W - 10) * 3 windows wholly inside the image (what
+ *     torchmetrics' reflection padding and crop leave); c1 = (0.01f * L)^2,
+ *     c2 = (0.03f * L)^2, L = max(pred_max - pred_min, truth_max - truth_min)
+ *     read from the record; ssim_sum = the sum of ((2 E[p] E[t] + c1)(2 s_pt +
+ *     c2)) / ((E[p]^2 + E[t]^2 + c1)(s_p + s_t + c2)), n_ssim the count.
+ *   mask (K in [1, 64], n_inst in [1, K]): logits [H*W,K], labels [H*W] int64
+ *     with -1 = unlabeled.  Probabilities as samnerf_present_frame's (softmax at
+ *     n_inst > 1: max, expf(z - max), the 32-lane tree sum, a second tree for
+ *     columns 32.. added to the first, division; else the sigmoid), the argmax
+ *     with the first index winning ties.  nll_sum = the sum over labeled
+ *     pixels of -logf(min(max(p[label], (float)epsilon), (float)(1 - epsilon))),
+ *     n_labeled their count.  inter[i] = #(argmax == i and label == i),
+ *     npred[i] = #(argmax == i), ntruth[i] = #(label == i) for i < n_classes
+ *     (<= 1024); a negative label matches no class.  overflow counts labels
+ *     outside [-1, K) and ids or labels >= n_classes: none is used as an index.
+ *     probs [H*W,K] and ids [H*W] are optional outputs.
+ *   SAM (h, w > 0): pred_feat [h*w,256] in the render's layout and gt_feat
+ *     [256,h*w], both read in place: feat_sq_sum = the sum of the fp32
+ *     (p - g)^2, n_feat = h*w*256.
+ * Every floating sum is in a fixed order: double partials per workgroup in the
+ * workspace, added in index order by one thread.  The histograms use integer
+ * atomics.  The same inputs give the same bits. */
+typedef struct {
+    double sq_sum;      uint64_t n_elem;
+    double nll_sum;     uint64_t n_labeled;
+    double ssim_sum;    uint64_t n_ssim;
+    double feat_sq_sum; uint64_t n_feat;
+    float pred_min, pred_max, truth_min, truth_max;
+    uint64_t overflow;
+    uint64_t reserved[5];
+} samnerf_eval_stats;              /* 128 bytes; uint32 hist[3][n_classes] follows */
+#define SAMNERF_EVAL_STATS_BYTES(n_classes) (128u + (((size_t)(n_classes) * 12u + 7u) & ~(size_t)7u))
+#define SAMNERF_EVAL_MAX_CLASSES 1024
+#define SAMNERF_EVAL_MAX_K 64
+
+typedef struct {
+    uint32_t H, W;                 /* the view; H*W pixels of the RGB and mask parts */
+    uint32_t C;                    /* channels of truth: 3 or 4; 0 = no RGB part */
+    uint32_t ssim;                 /* nonzero: the SSIM sum as well */
+    uint32_t K, n_inst;            /* K = 0: no mask part */
+    uint32_t n_classes;            /* bins of each histogram */
+    uint32_t h, w;                 /* the feature map; 0 = no SAM part */
+    float bg_color;
+    double epsilon;                /* opt.epsilon */
+    const float* pred_rgb;         /* [H*W,3] */
+    const float* truth;            /* [H*W,C] */
+    const float* logits;           /* [H*W,K] */
+    const int64_t* labels;         /* [H*W] */
+    const float* pred_feat;        /* [h*w,256] */
+    const float* gt_feat;          /* [256,h*w] */
+    uint8_t* pred_u8;              /* [H*W,3] or NULL */
+    uint8_t* truth_u8;             /* [H*W,3] or NULL */
+    uint8_t* error_u8;             /* [H*W] or NULL */
+    float* truth_out;              /* [H*W,3] or NULL */
+    float* probs;                  /* [H*W,K] or NULL */
+    int64_t* ids;                  /* [H*W] or NULL */
+    void* stats;                   /* the record: SAMNERF_EVAL_STATS_BYTES(n_classes) */
+    void* workspace;
+    size_t workspace_bytes;
+} samnerf_eval_args;
+
+/* *bytes: the workspace one call needs (the partial sums). */
+int samnerf_eval_workspace_size(const samnerf_eval_args* args, size_t* bytes);
+
+/* SAMNERF_EINVAL: no part asked for, a null pointer a part needs, C outside
+ * {0, 3, 4}, ssim without the RGB part or with H or W below 11, K above 64,
+ * n_inst outside [1, K], n_classes outside [1, 1024] with a mask part, a size of
+ * 2^31 values or more, stats not 8-byte aligned; SAMNERF_EWORKSPACE. */
+int samnerf_eval_frame(const samnerf_eval_args* args, samnerf_stream_t stream);
+
+/* The three histograms and the overflow count alone, from ready-made id maps
+ * (MeanIoUMeter.update): pred_ids, truth_ids [n] int64, stats a record as
+ * above, written whole. */
+int samnerf_eval_confusion(const int64_t* pred_ids, const int64_t* truth_ids, uint32_t n, uint32_t n_classes,
+                           void* stats, samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@
 #include <cmath>
 
 #include "samnerf_common.h"
+#include "softmax_sum.h"
 
 using namespace samnerf;
 
@@ -104,19 +105,7 @@ struct Params {
     int64_t* ids;
 };
 
-// The sum of t[0..32) as the tree of a 32-lane butterfly: t[i] += t[i + off] for
-// off = 16, 8, 4, 2, 1.  With the entries past K zero this is the order of
-// ATen's softmax kernels on the GPU (one lane per instance, next_pow2(K)
-// lanes, xor-shuffles), so the step's softmax and its backward give the bits
-// the torch ops of mask_train_step give.  Static indices: t stays in VGPRs.
-__device__ __forceinline__ float tree_sum32(float (&t)[kMaxK]) {
-#pragma unroll
-    for (uint32_t off = kMaxK / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t i = 0; i < off; ++i) t[i] += t[i + off];
-    }
-    return t[0];
-}
+static_assert(kMaxK == kTreeLanes, "tree_sum32 (softmax_sum.h) sums kMaxK entries");
 
 __global__ void __launch_bounds__(kT) k_ml_rows(Params P) {
     const uint32_t i = blockIdx.x * kT + threadIdx.x;

@@ -35,6 +35,7 @@
 #include <cmath>
 
 #include "samnerf_common.h"
+#include "softmax_sum.h"
 
 using namespace samnerf;
 
@@ -65,14 +66,7 @@ struct Params {
     float* parts;                             // [n_parts][3]: min, max, any NaN
 };
 
-__device__ __forceinline__ float tree_sum32(float (&t)[kMaxK]) {   // mask_loss.hip's
-#pragma unroll
-    for (uint32_t off = kMaxK / 2; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t i = 0; i < off; ++i) t[i] += t[i + off];
-    }
-    return t[0];
-}
+static_assert(kMaxK == kTreeLanes, "tree_sum32 (softmax_sum.h) sums kMaxK entries");
 
 // Python's a[lo:hi] on an axis of n: whether index v is selected
 __device__ __forceinline__ bool in_slice(int v, int lo, int hi, int n) {

@@ -90,6 +90,15 @@ class SamnerfPresentArgs(ctypes.Structure):
                 ("points", _vp), ("buffer", _vp), ("probs", _vp), ("ids", _vp), ("depth_out", _vp)]
 
 
+class SamnerfEvalArgs(ctypes.Structure):
+    """samnerf_eval_args (include/samnerf_hip.h)."""
+    _fields_ = [("H", _u32), ("W", _u32), ("C", _u32), ("ssim", _u32), ("K", _u32), ("n_inst", _u32),
+                ("n_classes", _u32), ("h", _u32), ("w", _u32), ("bg_color", _f32), ("epsilon", _f64),
+                ("pred_rgb", _vp), ("truth", _vp), ("logits", _vp), ("labels", _vp), ("pred_feat", _vp),
+                ("gt_feat", _vp), ("pred_u8", _vp), ("truth_u8", _vp), ("error_u8", _vp), ("truth_out", _vp),
+                ("probs", _vp), ("ids", _vp), ("stats", _vp), ("workspace", _vp), ("workspace_bytes", _sz)]
+
+
 _SIGS = {
     "samnerf_diag_variants": ([], _int),
     "samnerf_version": ([], ctypes.c_char_p),
@@ -164,6 +173,9 @@ _SIGS = {
                                  ctypes.POINTER(_f32)], _int),
     "samnerf_present_workspace_size": ([ctypes.POINTER(SamnerfPresentArgs)], _sz),
     "samnerf_present_frame": ([ctypes.POINTER(SamnerfPresentArgs), _vp, _sz, _vp], _int),
+    "samnerf_eval_workspace_size": ([ctypes.POINTER(SamnerfEvalArgs), ctypes.POINTER(_sz)], _int),
+    "samnerf_eval_frame": ([ctypes.POINTER(SamnerfEvalArgs), _vp], _int),
+    "samnerf_eval_confusion": ([_vp, _vp, _u32, _u32, _vp, _vp], _int),
 }
 
 
