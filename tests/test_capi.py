@@ -142,3 +142,23 @@ def test_mask_train_workspace_size_is_model_aware(hip_lib):
     for kind in (1, 2):
         m.mask_kind = kind
         assert hip_lib.samnerf_mask_train_workspace_size_model(ctypes.byref(m), n) == 2 * 7 * 96 * 4 * n
+
+
+def test_mask_train_workspace_size_steps_by_1024_rows(hip_lib):
+    """The 'default' head's saved activations are [units][Rp] with Rp = 32 N
+    rounded up to SAMNERF_MT_CHUNK = 1,024 rows -- k_mt_dw takes whole chunks
+    and the forward / backward kernels write the pad rows: the size is the
+    same for N = 1 .. 32 and strictly larger at N = 33; the adaptive heads'
+    stays 2 x 7 x 96 floats per ray."""
+    from samnerf_amd._lib import SamnerfModel
+    m = SamnerfModel()
+    m.with_mask = 1
+    m.mask_kind = 0
+    size = [hip_lib.samnerf_mask_train_workspace_size_model(ctypes.byref(m), n) for n in range(1, 34)]
+    assert len(set(size[:32])) == 1 and size[32] > size[0]
+    # one more chunk of every saved array: x 144, h1 / h2 / g2 / g1 256 each, o / go 32 each
+    assert size[32] - size[0] == (144 + 4 * 256 + 2 * 32) * 1024 * 4
+    for kind in (1, 2):
+        m.mask_kind = kind
+        for n in (1, 32, 33, 37):
+            assert hip_lib.samnerf_mask_train_workspace_size_model(ctypes.byref(m), n) == 2 * 7 * 96 * 4 * n

@@ -250,15 +250,16 @@ GRAD_TOL = 1e-4          # tests/test_gpu_mask_train.py's: relative, per tensor 
 #                          another order, float atomics in the 'default' head's scatter)
 
 
-def _step_inputs(cuda, K, seed):
-    """32 x 32 global rays and two 16 x 16 local patches, as the reference's
-    data dict (get_rays' keys), on the CPU."""
+def _step_inputs(cuda, K, seed, n_global=1024, patch=16):
+    """32 x 32 global rays (the first n_global of them) and two patch x patch
+    local patches, as the reference's data dict (get_rays' keys), on the CPU."""
     from test_gpu_mask_train import _rays
     g = torch.Generator().manual_seed(seed)
-    parts = [_rays(32, 4), _rays(16, 5), _rays(16, 6)]
+    parts = [_rays(32, 4), _rays(patch, 5), _rays(patch, 6)]
+    parts[0] = (parts[0][0][:n_global], parts[0][1][:n_global])
     ro = torch.cat([p[0] for p in parts]).contiguous()
     rd = torch.cat([p[1] for p in parts]).contiguous()
-    N, n, M = ro.shape[0], 1024, 16
+    N, n, M = ro.shape[0], n_global, 16
     masks = torch.randint(0, K, (1, N), generator=g)
     masks[0, n:][torch.rand(N - n, generator=g) < 0.3] = -1
     inc = torch.rand(N, generator=g)
@@ -267,14 +268,14 @@ def _step_inputs(cuda, K, seed):
     return data, torch.rand(2, M * M, generator=g), n
 
 
-def _full_opts(opt, n):
+def _full_opts(opt, n, patch=16, num_sample=20, label_reg=0.1):
     opt.num_rays, opt.adaptive_num_rays = n, False
-    opt.mixed_sampling, opt.num_local_sample, opt.local_sample_patch_size = True, 2, 16
+    opt.mixed_sampling, opt.num_local_sample, opt.local_sample_patch_size = True, 2, patch
     opt.rgb_similarity_loss_weight, opt.rgb_similarity_threshold = 5.0, 0.15
-    opt.rgb_similarity_num_sample, opt.rgb_similarity_iter, opt.rgb_similarity_exp_weight = 20, -1, 10.0
+    opt.rgb_similarity_num_sample, opt.rgb_similarity_iter, opt.rgb_similarity_exp_weight = num_sample, -1, 10.0
     opt.rgb_similarity_use_pred_logistics = False
     opt.error_map, opt.incoherent_uncertainty_weight = True, 0.5
-    opt.label_regularization_weight, opt.patch_size = 0.1, 4
+    opt.label_regularization_weight, opt.patch_size = label_reg, 4
 
 
 def _nets(cuda, head):
@@ -282,22 +283,18 @@ def _nets(cuda, head):
     return _mask_nets(cuda, n_inst=5) if head == "default" else _adaptive_nets(cuda, "density", 5)
 
 
-@pytest.mark.parametrize("head", ["default", "adaptive"])
-def test_full_step_matches_the_cpu_model(hip_lib, cuda, head, monkeypatch):
-    """mask_train_step_full with every term on (train_mask.sh's flags plus the
-    re-weighting and the label regularisation): the HIP step against the CPU
-    model's, which runs the reference's torch ops, at the HIP path's own bins
-    and with the same RGB-similarity draw."""
+def _full_step_against_the_cpu_model(cuda, head, monkeypatch, n_global=1024, patch=16, num_sample=20,
+                                     label_reg=0.1):
     from oracle_backend import injected_bins, oracle_encoders
     from test_gpu_mask_train import _fused_bins, _grad_errors
 
     import samnerf_amd.mask_loss as ml
     from samnerf_amd.train import mask_train_step_full
     gpu, cpu = _nets(cuda, head)
-    data, emap, n = _step_inputs(cuda, 5, seed=11)
+    data, emap, n = _step_inputs(cuda, 5, seed=11, n_global=n_global, patch=patch)
     for net in (gpu, cpu):
-        _full_opts(net.opt, n)
-    draw = ml.draw_similarity_samples(data["error_maps"][n:].view(2, 256), 20,
+        _full_opts(net.opt, n, patch, num_sample, label_reg)
+    draw = ml.draw_similarity_samples(data["error_maps"][n:].view(2, patch * patch), num_sample,
                                       generator=torch.Generator().manual_seed(12))
     monkeypatch.setattr(ml, "draw_similarity_samples", lambda inc, s, generator=None: draw.to(inc.device))
     gdata = {k: (v.to(cuda) if torch.is_tensor(v) else v) for k, v in data.items()}
@@ -316,6 +313,29 @@ def test_full_step_matches_the_cpu_model(hip_lib, cuda, head, monkeypatch):
     assert errs and not {k: v for k, v in errs.items() if v > GRAD_TOL}, errs
     assert (emap_g.cpu() - emap_c).abs().max() <= 1e-5 and not torch.equal(emap_c, emap)
     assert torch.equal(gt.cpu(), data["masks"]) and pred.shape == (data["rays_o"].shape[0],)
+    return cpu
+
+
+@pytest.mark.parametrize("head", ["default", "adaptive"])
+def test_full_step_matches_the_cpu_model(hip_lib, cuda, head, monkeypatch):
+    """mask_train_step_full with every term on (train_mask.sh's flags plus the
+    re-weighting and the label regularisation): the HIP step against the CPU
+    model's, which runs the reference's torch ops, at the HIP path's own bins
+    and with the same RGB-similarity draw."""
+    _full_step_against_the_cpu_model(cuda, head, monkeypatch)
+
+
+def test_full_step_at_a_ragged_total(hip_lib, cuda, monkeypatch):
+    """The whole step on the 'default' head at 37 global rays + 2 patches of
+    3 x 3 = 55 rays (R = 1,760 rows of Rp = 2,048: pad rows in k_mt_fwd /
+    k_mt_bwd / k_mt_dw, workgroups that straddle sample indices), 5 drawn
+    samples per patch: test_full_step_matches_the_cpu_model's assertions.  The
+    label regularisation is off: it views the rays as whole 4 x 4 patches
+    (utils.py:848), which 55 rays are not (the reference raises there, and so
+    does mask_loss)."""
+    cpu = _full_step_against_the_cpu_model(cuda, "default", monkeypatch, n_global=37, patch=3, num_sample=5,
+                                           label_reg=0.0)
+    assert all(float(p.grad.norm()) > 0 for p in cpu.parameters() if p.grad is not None)
 
 
 @pytest.mark.parametrize("head", ["default", "adaptive"])

@@ -20,10 +20,10 @@ pytestmark = pytest.mark.gpu
 GRAD_TOL = 1e-4          # relative, per tensor: fp32 sums in another order, float atomics
 
 
-def _mask_nets(cuda, n_inst=5, redundant=0, sum_after=False, seed=21, head_mode=1):
+def _mask_nets(cuda, n_inst=5, redundant=0, sum_after=False, seed=21, head_mode=1, m_grid_log2=12):
     spec = synth.ModelSpec(with_sam=False, with_mask=True, mask_type="default", n_inst=n_inst,
                            redundant_instance=redundant, sum_after_mlp=sum_after, grid_log2=12,
-                           prop_log2=10, m_grid_log2=12)
+                           prop_log2=10, m_grid_log2=m_grid_log2)
     params = synth.make_params(spec, seed=seed, emb_scale=0.5)
     gpu = make_net(spec, params, cuda).train()
     cpu = make_net(spec, params, "cpu").train()
@@ -62,11 +62,13 @@ def _grad_errors(gpu, cpu):
 
 @pytest.mark.parametrize("n_inst,redundant,sum_after,head_mode",
                          [(5, 0, False, 1), (2, 0, True, 1), (32, 0, False, 1), (1, 0, False, 1),
-                          (5, 0, False, 0), (32, 0, False, 0), (2, 0, True, 0)])
+                          (5, 0, False, 0), (32, 0, False, 0), (2, 0, True, 0),
+                          (17, 0, False, 1), (17, 0, False, 0)])
 def test_fused_mask_step_matches_cpu_twin(hip_lib, cuda, n_inst, redundant, sum_after, head_mode):
     """head_mode 1: the exact fp32 training forward (k_mt_fwd); 0 (the
     default): the f16x3 forward (k_mt_fwd16); the backward is exact fp32 in
-    both."""
+    both.  K = 17 fills one row of the last layer's second 16-row output tile
+    (K = 1, 2, 5 use the first tile alone, K = 32 both in full)."""
     from oracle_backend import injected_bins, oracle_encoders
     from samnerf_amd.train import mask_train_step
     gpu, cpu = _mask_nets(cuda, n_inst, redundant, sum_after, head_mode=head_mode)

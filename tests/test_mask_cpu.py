@@ -57,3 +57,27 @@ def test_mask_state_dict_keys_are_the_references():
         groups = net.get_params(1e-2)
         n = sum(p.numel() for g in groups for p in g["params"])
         assert n == sum(p.numel() for p in net.parameters()), (mt, at)
+
+
+@pytest.mark.parametrize("head", ["default", "density"])
+def test_mask_step_cpu_twin_is_close_to_its_float64_twin(oracle_lib, head):
+    """The references of the GPU tests against each other, without a GPU: the
+    fp32 CPU twin of mask_train_step (C oracle encoders, autograd) is within
+    1e-4 relative of the float64 twin (oracle_backend.float64_twin at the fp32
+    run's recorded sample positions) for every trained tensor and 2e-6 on the
+    loss, at 37 rays with a per-ray cam_near_far; float64_twin itself raises
+    unless every recorded encoder call is replayed (none left, none drifted),
+    and the fp32 twin's gradients are non-zero."""
+    from mask_train_fixtures import float64_twin_errors, ragged_batch
+    from test_gpu_mask_train import _adaptive_nets, _mask_nets
+    _, cpu = _mask_nets("cpu", 5) if head == "default" else _adaptive_nets("cpu", "density", 5)
+    ro, rd, gt, cnf = ragged_batch(37, 5)
+    errs, loss64, loss32 = float64_twin_errors({}, cpu, ro, rd, gt, cnf)
+    e = errs["cpu_fp32"]
+    print(head, "fp32 twin vs float64 twin:", {k: f"{v:.1e}" for k, v in e.items()})
+    want = ({"m_grid.embeddings"} | {f"mask_mlp.0.net.{i}.weight" for i in range(3)} if head == "default"
+            else {f"mask_mlp.{i}.weight" for i in range(6)})
+    assert set(e) == want
+    assert all(float(p.grad.norm()) > 0 for k, p in cpu.named_parameters() if k in want)
+    assert max(e.values()) <= 1e-4, e
+    assert abs(loss32 - loss64) <= 2e-6 * abs(loss64)
