@@ -1013,6 +1013,69 @@ int samnerf_eval_frame(const samnerf_eval_args* args, samnerf_stream_t stream);
 int samnerf_eval_confusion(const int64_t* pred_ids, const int64_t* truth_ids, uint32_t n, uint32_t n_classes,
                            void* stats, samnerf_stream_t stream);
 
+/* ------------------------------------------------------ incoherent masks --
+ * The incoherent-region table of --with_mask training ([n_img, cells] bool: the
+ * sampler's local patches are drawn from it and the loss weights its rays by
+ * it).  The reference builds it from the ground-truth masks at load
+ * (colmap_provider.py:798-801) and, under --use_dynamic_incoherent, from the
+ * mask head's own renders (Trainer.update_incoherent_mask, nerf/utils.py:1757-
+ * 1780).  Two entry points, no model, no workspace, nothing on the host:
+ *
+ * samnerf_incoherent_ids: render_mask (utils.py:1716-1737) and the argmax of
+ * update_incoherent_mask, per ray.  logits [N, K], K = n_inst +
+ * redundant_instance in [1, 32].  n_inst > 1: the softmax over the K columns
+ * (max, expf(z - max), the 32-lane tree sum, division: samnerf_mask_loss's),
+ * pred = [p[0] + .. + p[K-2] by the same tree, p[K-1]], and the id is
+ * argmax(pred): 1 where pred[1] > pred[0], else 0 -- a tie gives 0, and so does
+ * a NaN or infinite logit (every probability is then NaN).  n_inst == 1 (K ==
+ * 1): the id is 0 (an argmax over one column) and pred = [sigmoid(z)].
+ * ids [N] bytes; pred_mask [N, 2] ([N, 1] at n_inst == 1) fp32, optional.
+ *
+ * samnerf_incoherent_masks: get_incoherent_mask (utils.py:283-298) for n views
+ * in one launch.  masks [n, H, W]: int64 (the dataset's [n,H,W,1]) or the bytes
+ * of samnerf_incoherent_ids; values in [0, 2^14).  In fp32: bilinear down to
+ * (H / sfact, W / sfact), bilinear back up, |mask - recovered|, bilinear down
+ * again, cells >= 0.01f set to 1, and with keep_size nearest up to (H, W); the
+ * resizes are ATen's with align_corners = false: source index
+ * max(scale * (dst + 0.5) - 0.5, 0), upper neighbour clamped at the border;
+ * nearest min(floor(dst * scale), in - 1).  uncertain: that float map; table:
+ * 1 byte per cell, uncertain != 0 (the reference's .to(torch.bool): a residue
+ * below 0.01 that is not zero is True).  Both [n, H * W] with keep_size, else
+ * [n, (H / sfact) * (W / sfact)]; either may be NULL, not both.
+ * H and W must be divisible by sfact, a power of two: every product and sum is
+ * then exact in fp32, and the result equals the reference's on any device bit
+ * for bit.  At other sizes the reference's bool is the rounding residue of
+ * ATen's own kernels, which no other kernel reproduces: SAMNERF_EINVAL.  A
+ * workgroup takes SAMNERF_INCOHERENT_TILE^2 coarse cells of one view. */
+enum { SAMNERF_INCOHERENT_INT64 = 0, SAMNERF_INCOHERENT_UINT8 = 1 };
+#define SAMNERF_INCOHERENT_TILE 16
+
+typedef struct {
+    uint32_t N, K, n_inst;
+    const float* logits;           /* [N,K] */
+    uint8_t* ids;                  /* [N] */
+    float* pred_mask;              /* [N,2], [N,1] at n_inst == 1, or NULL */
+} samnerf_incoherent_ids_args;
+
+/* SAMNERF_EINVAL: null args, logits or ids, K outside [1, 32], n_inst outside
+ * [1, K], n_inst == 1 with K > 1.  N == 0 is a successful no-op. */
+int samnerf_incoherent_ids(const samnerf_incoherent_ids_args* args, samnerf_stream_t stream);
+
+typedef struct {
+    uint32_t n, H, W;              /* views and their size */
+    uint32_t sfact;                /* a power of two dividing H and W */
+    int32_t keep_size;             /* nonzero: outputs at H x W */
+    int32_t input_type;            /* SAMNERF_INCOHERENT_INT64 / _UINT8 */
+    const void* masks;             /* [n,H,W] */
+    uint8_t* table;                /* [n, cells] or NULL */
+    float* uncertain;              /* [n, cells] or NULL */
+} samnerf_incoherent_masks_args;
+
+/* SAMNERF_EINVAL: null args or masks, table and uncertain both NULL, sfact not
+ * a power of two, H or W not divisible by sfact, H / sfact or W / sfact == 0,
+ * H * W of 2^31 or more, an unknown input_type.  n == 0 is a successful no-op. */
+int samnerf_incoherent_masks(const samnerf_incoherent_masks_args* args, samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

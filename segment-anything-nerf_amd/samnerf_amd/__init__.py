@@ -4,5 +4,6 @@
   fused     FusedRenderer: NeRFRenderer.run as five fused kernel launches
   dist      ray sharding over ranks + RCCL all-gather of output tiles
   batch     TrainBatchSampler: a training step's ray choice and collate gathers
+  incoherent  the incoherent-region tables: from the GT masks, and the dynamic update
 """
 from ._lib import EXPORTED, LIB_PATH, SamnerfUnavailable, lib  # noqa: F401

@@ -99,6 +99,17 @@ class SamnerfEvalArgs(ctypes.Structure):
                 ("probs", _vp), ("ids", _vp), ("stats", _vp), ("workspace", _vp), ("workspace_bytes", _sz)]
 
 
+class SamnerfIncoherentIdsArgs(ctypes.Structure):
+    """samnerf_incoherent_ids_args (include/samnerf_hip.h)."""
+    _fields_ = [("N", _u32), ("K", _u32), ("n_inst", _u32), ("logits", _vp), ("ids", _vp), ("pred_mask", _vp)]
+
+
+class SamnerfIncoherentMasksArgs(ctypes.Structure):
+    """samnerf_incoherent_masks_args (include/samnerf_hip.h)."""
+    _fields_ = [("n", _u32), ("H", _u32), ("W", _u32), ("sfact", _u32), ("keep_size", ctypes.c_int32),
+                ("input_type", ctypes.c_int32), ("masks", _vp), ("table", _vp), ("uncertain", _vp)]
+
+
 _SIGS = {
     "samnerf_diag_variants": ([], _int),
     "samnerf_version": ([], ctypes.c_char_p),
@@ -176,6 +187,8 @@ _SIGS = {
     "samnerf_eval_workspace_size": ([ctypes.POINTER(SamnerfEvalArgs), ctypes.POINTER(_sz)], _int),
     "samnerf_eval_frame": ([ctypes.POINTER(SamnerfEvalArgs), _vp], _int),
     "samnerf_eval_confusion": ([_vp, _vp, _u32, _u32, _vp, _vp], _int),
+    "samnerf_incoherent_ids": ([ctypes.POINTER(SamnerfIncoherentIdsArgs), _vp], _int),
+    "samnerf_incoherent_masks": ([ctypes.POINTER(SamnerfIncoherentMasksArgs), _vp], _int),
 }
 
 
