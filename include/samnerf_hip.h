@@ -850,10 +850,13 @@ int samnerf_batch_draw_host(uint64_t seed, uint64_t offset, uint32_t item, uint3
  * the render, in fp32 with every product and sum rounded on its own, in the
  * reference's op order.  No model: it works on any render's outputs.  In order:
  *   1. logits [rH*rW, K] (K = n_inst + redundant_instance in [1, 32]; K = 0: no
- *      mask view): n_inst > 1 the softmax over the K columns (max, expf(z - max),
- *      the 32-lane tree sum, division: samnerf_mask_loss's), n_inst == 1 the
- *      sigmoid; then the largest probability and its index, the first index
- *      winning ties;
+ *      mask view): the instance row.  n_inst > 1 the softmax over the K columns
+ *      (max, expf(z - max), the sum as a 32-lane tree, expf(z - max) / sum),
+ *      n_inst == 1 the sigmoid 1 / (1 + expf(-z)); then the largest probability
+ *      and its index, the first index winning ties.  samnerf_mask_loss,
+ *      samnerf_eval_frame and samnerf_incoherent_ids run this same row (one
+ *      device function, csrc/instance_row.h), so their probabilities and ids
+ *      agree bit for bit;
  *   2. the colour.  render id = instance_id if 0 <= instance_id < n_inst, else -1.
  *      HEATMAP: color_map[id] * p[id], or color_map[argmax] * max at id -1;
  *      COMPOSITION: image * 0.7f + c * 0.3f with c = color_map[argmax], or c = image
@@ -943,10 +946,9 @@ int samnerf_present_frame(const samnerf_present_args* args, void* workspace, siz
  *     read from the record; ssim_sum = the sum of ((2 E[p] E[t] + c1)(2 s_pt +
  *     c2)) / ((E[p]^2 + E[t]^2 + c1)(s_p + s_t + c2)), n_ssim the count.
  *   mask (K in [1, 64], n_inst in [1, K]): logits [H*W,K], labels [H*W] int64
- *     with -1 = unlabeled.  Probabilities as samnerf_present_frame's (softmax at
- *     n_inst > 1: max, expf(z - max), the 32-lane tree sum, a second tree for
- *     columns 32.. added to the first, division; else the sigmoid), the argmax
- *     with the first index winning ties.  nll_sum = the sum over labeled
+ *     with -1 = unlabeled.  Probabilities and argmax: the instance row of
+ *     samnerf_present_frame (step 1), with a second tree for columns 32.. added
+ *     to the first where K > 32.  nll_sum = the sum over labeled
  *     pixels of -logf(min(max(p[label], (float)epsilon), (float)(1 - epsilon))),
  *     n_labeled their count.  inter[i] = #(argmax == i and label == i),
  *     npred[i] = #(argmax == i), ntruth[i] = #(label == i) for i < n_classes
@@ -1023,8 +1025,8 @@ int samnerf_eval_confusion(const int64_t* pred_ids, const int64_t* truth_ids, ui
  *
  * samnerf_incoherent_ids: render_mask (utils.py:1716-1737) and the argmax of
  * update_incoherent_mask, per ray.  logits [N, K], K = n_inst +
- * redundant_instance in [1, 32].  n_inst > 1: the softmax over the K columns
- * (max, expf(z - max), the 32-lane tree sum, division: samnerf_mask_loss's),
+ * redundant_instance in [1, 32].  n_inst > 1: the softmax of the instance row
+ * (samnerf_present_frame, step 1),
  * pred = [p[0] + .. + p[K-2] by the same tree, p[K-1]], and the id is
  * argmax(pred): 1 where pred[1] > pred[0], else 0 -- a tie gives 0, and so does
  * a NaN or infinite logit (every probability is then NaN).  n_inst == 1 (K ==

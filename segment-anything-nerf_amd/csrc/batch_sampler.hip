@@ -18,6 +18,7 @@
 // k_batch_draw_error's histograms, whose sums do not depend on their order.
 #include <float.h>
 
+#include "block_reduce.h"
 #include "philox.h"
 #include "samnerf_common.h"
 
@@ -205,15 +206,6 @@ __global__ void __launch_bounds__(256) k_batch_draw_patches(DrawArgs a) {
     a.pixels[t] = patch_pixel(x0, y0, k, a.p, a.W);
 }
 
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // Mode C (utils.py:180-194, :206-219): block b draws the centre of map row b
 // -- the cell of largest key, the lower cell winning a tie -- as a block
 // arg-max over (key bits, ~cell) packed in 64 bits, the row streamed from
@@ -242,12 +234,10 @@ __global__ void __launch_bounds__(256) k_batch_draw_centred(DrawArgs a) {
             best = v > best ? v : best;
         }
     }
-    best = wave_max_u64(best);
-    if ((tid & 63u) == 0u) wbest[tid >> 6] = best;
+    const auto larger = [](uint64_t a, uint64_t b) { return b > a ? b : a; };
+    waves_put(wave_all(best, larger), wbest);
     __syncthreads();
-    best = wbest[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) best = wbest[w] > best ? wbest[w] : best;
+    best = waves_fold(wbest, 4u, larger);
     const uint32_t c = 0xffffffffu - (uint32_t)best;          // < cells: every thread's candidates are
     const uint32_t crow = c / a.M, ccol = c % a.M;
     // utils.py:188-194: float32, the corner clamped to [0, H - p - 1]

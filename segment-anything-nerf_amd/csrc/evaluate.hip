@@ -9,15 +9,16 @@
 //
 // Sums follow mask_loss.hip's rule: every floating sum is a fixed-order sum.
 // A thread adds its own values in double in index order, the workgroup adds its
-// threads in a fixed tree, the partial goes to the workspace, and one thread of
+// threads in a fixed tree (block_reduce.h block_sum_ordered; min and max through
+// its order-free forms), the partial goes to the workspace, and one thread of
 // k_eval_finish adds the at most 1024 partials in index order.  No float
 // atomics; the histograms and counts use integer atomics (LDS, then global),
 // which commute.
 //
 //   k_eval_rgb     per pixel: the RGBA composite, (p - t)^2, min / max, the three
 //                  uint8 buffers
-//   k_eval_mask    per pixel: probabilities (present.hip's), argmax, NLL, the
-//                  three histograms
+//   k_eval_mask    per pixel: probabilities and argmax (instance_row.h's row, with
+//                  its second tree for K > 32), NLL, the three histograms
 //   k_eval_sam     64 x 64 (pixel, channel) tiles: (p - g)^2 with the [256, h*w]
 //                  truth transposed through LDS, both read in place
 //   k_eval_finish  the partials into the record (stage 0: all but SSIM)
@@ -33,8 +34,9 @@
 #include <cmath>
 #include <cstring>
 
+#include "block_reduce.h"
+#include "instance_row.h"
 #include "samnerf_common.h"
-#include "softmax_sum.h"
 
 using namespace samnerf;
 
@@ -43,7 +45,8 @@ namespace {
 constexpr uint32_t kT = 256;
 constexpr uint32_t kWaves = kT / 64;
 constexpr uint32_t kMaxParts = 1024;          // workgroups of every reducing kernel
-constexpr uint32_t kMaxK = SAMNERF_EVAL_MAX_K;
+constexpr uint32_t kMaxEvalK = SAMNERF_EVAL_MAX_K;   // two trees of instance_row.h's row
+static_assert(kMaxEvalK == 2 * kTreeLanes, "k_eval_mask's row has two trees");
 constexpr uint32_t kTaps = 11, kHalo = kTaps - 1;
 constexpr uint32_t kTW = 32, kTH = 16, kIW = kTW + kHalo, kIH = kTH + kHalo;
 constexpr uint32_t kFeat = 256, kFT = 64;     // SAM channels; the transposing tile's side
@@ -77,17 +80,12 @@ struct Params {
     Workspace* ws;
 };
 
-// the sum over the workgroup in a fixed tree; valid in thread 0
-__device__ double block_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double a = sh[0];
-    for (uint32_t w = 1; w < (blockDim.x >> 6); ++w) a += sh[w];
-    __syncthreads();
-    return a;
-}
+// min and max of the predictions and of the truth: slots 0 .. 3 of the order-free reductions
+struct MinMax {
+    __device__ __forceinline__ float operator()(uint32_t j, float a, float b) const {
+        return (j & 1u) ? fmaxf(a, b) : fminf(a, b);
+    }
+};
 
 // utils.py:1141-1145, channel ch of pixel g
 __device__ __forceinline__ float truth_of(const float* g, uint32_t C, uint32_t ch, float bg) {
@@ -125,23 +123,14 @@ __global__ void __launch_bounds__(kT) k_eval_rgb(Params P) {
             P.error_u8[i] = (uint8_t)(int)(((e0 + e1) + e2) / 3.0f);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        pmn = fminf(pmn, __shfl_xor(pmn, o, 64)); pmx = fmaxf(pmx, __shfl_xor(pmx, o, 64));
-        tmn = fminf(tmn, __shfl_xor(tmn, o, 64)); tmx = fmaxf(tmx, __shfl_xor(tmx, o, 64));
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        float* o = shf + 4 * (threadIdx.x >> 6);
-        o[0] = pmn; o[1] = pmx; o[2] = tmn; o[3] = tmx;
-    }
-    const double sq = block_sum(acc, shd);    // its barriers order shf as well
+    float mm[4] = {pmn, pmx, tmn, tmx};
+    wave_all(mm, MinMax{});
+    waves_put(mm, shf);
+    const double sq = block_sum_ordered(acc, shd);    // its barriers order shf as well
     if (threadIdx.x == 0) {
-        RgbPart r{sq, shf[0], shf[1], shf[2], shf[3]};
-        for (uint32_t w = 1; w < kWaves; ++w) {
-            r.pmin = fminf(r.pmin, shf[4 * w]); r.pmax = fmaxf(r.pmax, shf[4 * w + 1]);
-            r.tmin = fminf(r.tmin, shf[4 * w + 2]); r.tmax = fmaxf(r.tmax, shf[4 * w + 3]);
-        }
-        P.ws->rgb[blockIdx.x] = r;
+        float r[4] = {shf[0], shf[1], shf[2], shf[3]};
+        waves_fold(r, shf, kWaves, MinMax{});
+        P.ws->rgb[blockIdx.x] = RgbPart{sq, r[0], r[1], r[2], r[3]};
     }
 }
 
@@ -180,34 +169,11 @@ __global__ void __launch_bounds__(kT) k_eval_mask(Params P) {
     for (uint32_t chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
         const uint32_t base = chunk * T, cnt = min(T, P.n - base), i = base + t;
         __syncthreads();
-        for (uint32_t e = t; e < cnt * K; e += T) {
-            const uint32_t row = e / K;
-            sz[row * Kp + (e - row * K)] = P.logits[(size_t)base * K + e];
-        }
+        rows_to_tile(sz, P.logits, (size_t)base * K, cnt, K, Kp, T);
         __syncthreads();
         if (t < cnt) {
             float* z = sz + t * Kp;
-            if (P.n_inst > 1) {
-                float mx = z[0];
-                for (uint32_t k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-                float tr[kTreeLanes];
-#pragma unroll
-                for (uint32_t k = 0; k < kTreeLanes; ++k) tr[k] = k < K ? expf(z[k] - mx) : 0.0f;
-                float sum = tree_sum32(tr);
-                if (K > kTreeLanes) {
-#pragma unroll
-                    for (uint32_t k = 0; k < kTreeLanes; ++k)
-                        tr[k] = kTreeLanes + k < K ? expf(z[kTreeLanes + k] - mx) : 0.0f;
-                    sum += tree_sum32(tr);
-                }
-                for (uint32_t k = 0; k < K; ++k) z[k] = expf(z[k] - mx) / sum;
-            } else {
-                for (uint32_t k = 0; k < K; ++k) z[k] = 1.0f / (1.0f + expf(-z[k]));
-            }
-            float best = -1.0f;
-            uint32_t arg = 0;
-            for (uint32_t k = 0; k < K; ++k)
-                if (z[k] > best) { best = z[k]; arg = k; }     // the first index wins ties
+            const uint32_t arg = instance_row<2>(z, K, P.n_inst).arg;
             if (P.ids) P.ids[i] = (int64_t)arg;
             const int64_t label = P.labels[i];
             hist_add(hist, nc, (int64_t)arg, label, &hist[3 * nc]);
@@ -222,15 +188,11 @@ __global__ void __launch_bounds__(kT) k_eval_mask(Params P) {
             }
         }
         __syncthreads();
-        if (P.probs)
-            for (uint32_t e = t; e < cnt * K; e += T) {
-                const uint32_t row = e / K;
-                P.probs[(size_t)base * K + e] = sz[row * Kp + (e - row * K)];
-            }
+        if (P.probs) tile_to_rows(P.probs, (size_t)base * K, sz, cnt, K, Kp, T);
     }
     __syncthreads();
     hist_flush(P, hist);
-    const double s = block_sum(acc, shd);
+    const double s = block_sum_ordered(acc, shd);
     if (t == 0) P.ws->nll[blockIdx.x] = s;
 }
 
@@ -265,7 +227,7 @@ __global__ void __launch_bounds__(kT) k_eval_sam(Params P) {
             acc += (double)(d * d);
         }
     }
-    const double s = block_sum(acc, shd);
+    const double s = block_sum_ordered(acc, shd);
     if (t == 0) P.ws->feat[blockIdx.x] = s;
 }
 
@@ -330,7 +292,7 @@ __global__ void __launch_bounds__(kT) k_eval_ssim(Params P) {
             acc += (double)v;
         }
     }
-    const double s = block_sum(acc, shd);
+    const double s = block_sum_ordered(acc, shd);
     if (t == 0) P.ws->ssim[blockIdx.x] = s;
 }
 
@@ -363,27 +325,18 @@ __global__ void __launch_bounds__(kT) k_eval_finish(Params P, int stage) {
     }
     for (uint32_t b = t; b < P.n_mask; b += kT) sh[1][b] = P.ws->nll[b];
     for (uint32_t b = t; b < P.n_feat; b += kT) sh[2][b] = P.ws->feat[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        pmn = fminf(pmn, __shfl_xor(pmn, o, 64)); pmx = fmaxf(pmx, __shfl_xor(pmx, o, 64));
-        tmn = fminf(tmn, __shfl_xor(tmn, o, 64)); tmx = fmaxf(tmx, __shfl_xor(tmx, o, 64));
-    }
-    if ((t & 63u) == 0) {
-        float* o = shf + 4 * (t >> 6);
-        o[0] = pmn; o[1] = pmx; o[2] = tmn; o[3] = tmx;
-    }
+    float mm[4] = {pmn, pmx, tmn, tmx};
+    wave_all(mm, MinMax{});
+    waves_put(mm, shf);
     __syncthreads();
     if (t == 0 && P.n_rgb) {
         double a = 0.0;
 #pragma unroll 16
         for (uint32_t b = 0; b < P.n_rgb; ++b) a += sh[0][b];
-        for (uint32_t w = 1; w < kWaves; ++w) {
-            pmn = fminf(pmn, shf[4 * w]); pmx = fmaxf(pmx, shf[4 * w + 1]);
-            tmn = fminf(tmn, shf[4 * w + 2]); tmx = fmaxf(tmx, shf[4 * w + 3]);
-        }
+        waves_fold(mm, shf, kWaves, MinMax{});         // thread 0 holds wave 0's
         S->sq_sum = a;
         S->n_elem = (uint64_t)P.n * 3;
-        S->pred_min = pmn; S->pred_max = pmx; S->truth_min = tmn; S->truth_max = tmx;
+        S->pred_min = mm[0]; S->pred_max = mm[1]; S->truth_min = mm[2]; S->truth_max = mm[3];
     }
     if (t == 64 && P.n_mask) {
         double a = 0.0;
@@ -423,7 +376,7 @@ const char* validate(const samnerf_eval_args* a) {
         if (a->H < kTaps || a->W < kTaps) return "SSIM needs H, W >= 11: one whole window";
     }
     if (mask) {
-        if (a->K > kMaxK) return "K (n_inst + redundant_instance) must lie in [1, 64]";
+        if (a->K > kMaxEvalK) return "K (n_inst + redundant_instance) must lie in [1, 64]";
         if (a->n_inst < 1 || a->n_inst > a->K) return "n_inst must lie in [1, K]";
         if (a->n_classes < 1 || a->n_classes > SAMNERF_EVAL_MAX_CLASSES) return "n_classes must lie in [1, 1024]";
         if (!a->logits || !a->labels) return "the mask part needs logits and labels";

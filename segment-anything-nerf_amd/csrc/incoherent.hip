@@ -7,8 +7,8 @@
 // :1716-1737, and get_incoherent_mask, :283-298).
 //
 //   k_incoherent_ids    per rendered ray: render_mask's softmax over the K
-//                       instance columns, pred = [sum of the first K - 1, last],
-//                       and the argmax of those two as a byte
+//                       instance columns (instance_row.h), pred = [sum of the
+//                       first K - 1, last], and the argmax of those two as a byte
 //   k_incoherent_masks  the whole get_incoherent_mask chain for n views in one
 //                       launch: bilinear down by sfact, bilinear back up,
 //                       |mask - recovered|, bilinear down again, cells >= 0.01
@@ -35,19 +35,17 @@
 // the rounding residue of ATen's kernels; such sizes are refused here.
 #include <cmath>
 
+#include "instance_row.h"
 #include "samnerf_common.h"
-#include "softmax_sum.h"
 
 using namespace samnerf;
 
 namespace {
 
 constexpr uint32_t kT = 256;
-constexpr uint32_t kMaxK = 32;
 constexpr uint32_t kTile = SAMNERF_INCOHERENT_TILE;   // coarse cells per tile edge
 constexpr uint32_t kHalo = kTile + 2;
 
-static_assert(kMaxK == kTreeLanes, "tree_sum32 (softmax_sum.h) sums kMaxK entries");
 static_assert(kTile * kTile == kT, "one thread per coarse cell of the tile");
 
 // ------------------------------------------------------------------- ids --
@@ -64,26 +62,19 @@ __global__ void __launch_bounds__(kT) k_incoherent_ids(IdsParams P) {
     const uint32_t t = threadIdx.x, K = P.K, Kp = P.Kp;
     const size_t base = (size_t)blockIdx.x * kT;
     const uint32_t cnt = (uint32_t)min((size_t)kT, (size_t)P.N - base);
-    for (uint32_t e = t; e < cnt * K; e += kT) {
-        const uint32_t row = e / K;
-        sz[row * Kp + (e - row * K)] = P.logits[base * K + e];
-    }
+    rows_to_tile(sz, P.logits, base * K, cnt, K, Kp, kT);
     __syncthreads();
     if (t >= cnt) return;
     const float* z = sz + t * Kp;
     const size_t i = base + t;
     if (P.n_inst > 1) {
-        float mx = z[0];
-        for (uint32_t k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
+        const RowNorm n = row_norm<1>(z, K);
+        // inst_mask[..., :-1].sum(-1): the same tree over the first K - 1 probabilities
         float tr[kMaxK];
 #pragma unroll
-        for (uint32_t k = 0; k < kMaxK; ++k) tr[k] = k < K ? expf(z[k] - mx) : 0.0f;
-        const float sum = tree_sum32(tr);
-        // inst_mask[..., :-1].sum(-1): the same tree over the first K - 1 probabilities
-#pragma unroll
-        for (uint32_t k = 0; k < kMaxK; ++k) tr[k] = k + 1 < K ? expf(z[k] - mx) / sum : 0.0f;
+        for (uint32_t k = 0; k < kMaxK; ++k) tr[k] = k + 1 < K ? row_prob(z, k, n) : 0.0f;
         const float others = tree_sum32(tr);
-        const float last = expf(z[K - 1] - mx) / sum;
+        const float last = row_prob(z, K - 1, n);
         // argmax of [others, last]: 1 only where last is strictly greater; a
         // tie and a NaN (softmax of a NaN or infinite logit) give 0
         P.ids[i] = last > others ? 1 : 0;
@@ -91,7 +82,7 @@ __global__ void __launch_bounds__(kT) k_incoherent_ids(IdsParams P) {
     } else {
         // one column: the argmax over a dimension of size one
         P.ids[i] = 0;
-        if (P.pred) P.pred[i] = 1.0f / (1.0f + expf(-z[0]));
+        if (P.pred) P.pred[i] = row_sigmoid(z[0]);
     }
 }
 

@@ -8,10 +8,11 @@
 //
 // Everything is fp32 in the reference's op order per element.  Every sum runs
 // in an order fixed by the sizes alone: a ray's K values as a fixed tree
-// (tree_sum32: the softmax and its backward) or in index order, a
-// per-ray or per-patch partial stored to the workspace, and one 256-thread
-// workgroup (k_ml_reduce) that adds the partials strided by 256 and then as a
-// tree.  No float atomics: the same inputs give the same bits.
+// (instance_row.h: the softmax and, with the same tree_sum32, its backward) or
+// in index order, a per-ray or per-patch partial stored to the workspace, and
+// one 256-thread workgroup (k_ml_reduce) that adds the partials strided by 256
+// and then as a tree (block_reduce.h block_sum_tree).  No float atomics: the
+// same inputs give the same bits.
 //
 //   k_ml_rows    per ray: softmax p -> workspace, argmax, and for a global ray
 //                its NLL, the clamped q of its label and its error-map value
@@ -30,8 +31,9 @@
 // header): flagged per ray / counted per patch, summed into loss_terms[4].
 #include <cmath>
 
+#include "block_reduce.h"
+#include "instance_row.h"
 #include "samnerf_common.h"
-#include "softmax_sum.h"
 
 using namespace samnerf;
 
@@ -39,7 +41,7 @@ namespace {
 
 constexpr uint32_t kT = 256;                 // threads of every workgroup here
 constexpr uint32_t kWaves = kT / 64;
-constexpr uint32_t kMaxK = 32, kMaxQK = 8192, kMaxQ = 1024, kMaxS = 256;
+constexpr uint32_t kMaxQK = 8192, kMaxQ = 1024, kMaxS = 256;
 
 enum : uint32_t {
     F_LABELLED = 1u,      // label != -1
@@ -105,32 +107,25 @@ struct Params {
     int64_t* ids;
 };
 
-static_assert(kMaxK == kTreeLanes, "tree_sum32 (softmax_sum.h) sums kMaxK entries");
-
 __global__ void __launch_bounds__(kT) k_ml_rows(Params P) {
     const uint32_t i = blockIdx.x * kT + threadIdx.x;
     if (i >= P.N) return;
     const uint32_t K = P.K;
     const float* z = P.z + (size_t)i * K;
     float* p = P.p + (size_t)i * K;
-    float mx = z[0];
-    for (uint32_t k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-    float t[kMaxK];
-#pragma unroll
-    for (uint32_t k = 0; k < kMaxK; ++k) t[k] = k < K ? expf(z[k] - mx) : 0.0f;
-    const float sum = tree_sum32(t);
+    const RowNorm nrm = row_norm<1>(z, K);
     const int64_t g = P.labels[i];
     const bool label_ok = g >= 0 && g < (int64_t)K;
-    float best = -1.0f, pg = 0.0f, sq = 0.0f;
-    uint32_t arg = 0;
+    float pg = 0.0f, sq = 0.0f;
+    RowBest b;
     for (uint32_t k = 0; k < K; ++k) {
-        const float v = expf(z[k] - mx) / sum;
+        const float v = row_prob(z, k, nrm);
         p[k] = v;
-        if (v > best) { best = v; arg = k; }           // the first index wins ties
+        b.take(k, v);
         if (label_ok && k == (uint32_t)g) pg = v;
         sq += v * v;
     }
-    P.ids[i] = (int64_t)arg;
+    P.ids[i] = (int64_t)b.arg;
     uint32_t f = g != -1 ? F_LABELLED : 0u;
     if (i < P.n) {
         float nll = 0.0f, q = 0.0f;
@@ -201,12 +196,6 @@ __global__ void __launch_bounds__(kT) k_ml_lr(Params P) {
     o[0] = ax; o[1] = wx; o[2] = ay; o[3] = wy;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // One pixel r against one sample: whether their colours are similar, the
 // cosine c of p_r with the sample's mask and e = exp(-a c - epsilon).
 struct Pair { bool sim; float c, e; };
@@ -256,18 +245,17 @@ __global__ void __launch_bounds__(kT) k_ml_rgb(Params P) {
     }
     for (uint32_t s = t; s < S; s += kT) {
         const int j = ssamp[s];
-        int arg = 0, cnt = 0;
+        RowBest b;
+        int cnt = 0;
         if (j >= 0) {
-            float best = -1.0f;
-            for (uint32_t k = 0; k < K; ++k)
-                if (sp[j * K + k] > best) { best = sp[j * K + k]; arg = (int)k; }
+            for (uint32_t k = 0; k < K; ++k) b.take(k, sp[j * K + k]);
             for (uint32_t r = 0; r < Q; ++r) {          // an integer count: any order
                 const float dx = srgb[3 * r] - srgb[3 * j], dy = srgb[3 * r + 1] - srgb[3 * j + 1],
                             dz = srgb[3 * r + 2] - srgb[3 * j + 2];
                 cnt += sqrtf(dx * dx + dy * dy + dz * dz) < P.thr ? 1 : 0;
             }
         }
-        sarg[s] = arg;
+        sarg[s] = (int)b.arg;
         scnt[s] = cnt;
     }
     __syncthreads();
@@ -288,8 +276,7 @@ __global__ void __launch_bounds__(kT) k_ml_rgb(Params P) {
                 }
             }
         }
-        v = wave_sum(v);
-        if ((t & 63u) == 0) swp[s * kWaves + (t >> 6)] = v;
+        waves_put(wave_sum_down(v), swp + s * kWaves);
     }
     __syncthreads();
     if (t == 0) {
@@ -297,7 +284,7 @@ __global__ void __launch_bounds__(kT) k_ml_rgb(Params P) {
         uint32_t bad = 0;
         for (uint32_t s = 0; s < S; ++s) {
             if (ssamp[s] < 0) { ++bad; continue; }
-            const float v = (swp[s * kWaves] + swp[s * kWaves + 1]) + (swp[s * kWaves + 2] + swp[s * kWaves + 3]);
+            const float v = sum_waves4(swp + s * kWaves);
             tot += P.redundant ? v : v / (float)scnt[s];     // scnt >= 1: a sample is similar to itself
         }
         P.rgb_part[l] = tot;
@@ -336,15 +323,6 @@ __global__ void __launch_bounds__(kT) k_ml_rgb(Params P) {
     }
 }
 
-// the sum of v over the workgroup: the waves' trees, then the waves in order
-__device__ float block_sum(float v, float* sh) {
-    v = wave_sum(v);
-    __syncthreads();                                   // sh may still be read from the last call
-    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 __global__ void __launch_bounds__(kT) k_ml_reduce(Params P) {
     __shared__ float sh[kWaves];
     const uint32_t t = threadIdx.x;
@@ -359,20 +337,20 @@ __global__ void __launch_bounds__(kT) k_ml_reduce(Params P) {
             w += 1.0f - m + P.u * m;
         }
     }
-    nll = block_sum(nll, sh);
-    w = block_sum(w, sh);
-    labelled = block_sum(labelled, sh);
-    bad = block_sum(bad, sh);
+    nll = block_sum_tree(nll, sh);
+    w = block_sum_tree(w, sh);
+    labelled = block_sum_tree(labelled, sh);
+    bad = block_sum_tree(bad, sh);
     float ax = 0.0f, wx = 0.0f, ay = 0.0f, wy = 0.0f;
     if (P.lr_on) {
         for (uint32_t i = t; i < P.N; i += kT) {
             const float* o = P.lr + (size_t)4 * i;
             ax += o[0]; wx += o[1]; ay += o[2]; wy += o[3];
         }
-        ax = block_sum(ax, sh);
-        wx = block_sum(wx, sh);
-        ay = block_sum(ay, sh);
-        wy = block_sum(wy, sh);
+        ax = block_sum_tree(ax, sh);
+        wx = block_sum_tree(wx, sh);
+        ay = block_sum_tree(ay, sh);
+        wy = block_sum_tree(wy, sh);
     }
     if (t != 0) return;
     const bool any = labelled > 0.0f;

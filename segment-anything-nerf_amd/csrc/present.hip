@@ -9,9 +9,9 @@
 //
 // Everything is fp32, one rounding per product and sum, in the reference's op
 // order (the build's -ffp-contract=off keeps a * b + c two operations).  The
-// softmax is k_ml_rows' (mask_loss.hip): max, expf(z - max), the 32-lane tree
-// sum, division -- the bits of ATen's softmax on the GPU.  No float atomics:
-// min and max of the depth are order-free, two stages of fixed shape.
+// probabilities and their argmax are instance_row.h's row -- the bits of
+// ATen's softmax on the GPU.  No float atomics: min and max of the depth are
+// order-free (block_reduce.h), two stages of fixed shape.
 //
 // The click squares follow Python's slice rules, as the reference's
 // mask[y - r:y + r, x - r:x + r] applies them: an end past the image is
@@ -31,11 +31,13 @@
 // A [N,3] frame is 12-byte pixels: a workgroup moves its 256 pixels' 768
 // contiguous dwords between memory and LDS with lane = dword, and each thread
 // takes its pixel from LDS (stride 3: no bank conflict).  The logits and the
-// probabilities move the same way, the LDS row padded to an odd length.
+// probabilities move the same way, the LDS row padded to an odd length
+// (instance_row.h rows_to_tile / tile_to_rows).
 #include <cmath>
 
+#include "block_reduce.h"
+#include "instance_row.h"
 #include "samnerf_common.h"
-#include "softmax_sum.h"
 
 using namespace samnerf;
 
@@ -43,7 +45,6 @@ namespace {
 
 constexpr uint32_t kT = 256;
 constexpr uint32_t kWaves = kT / 64;
-constexpr uint32_t kMaxK = 32;
 constexpr uint32_t kMaxParts = 256;           // workgroups of k_present_minmax
 constexpr int kRadius = 2;                    // overlay_point's default
 
@@ -65,8 +66,6 @@ struct Params {
     float* depth_out;
     float* parts;                             // [n_parts][3]: min, max, any NaN
 };
-
-static_assert(kMaxK == kTreeLanes, "tree_sum32 (softmax_sum.h) sums kMaxK entries");
 
 // Python's a[lo:hi] on an axis of n: whether index v is selected
 __device__ __forceinline__ bool in_slice(int v, int lo, int hi, int n) {
@@ -108,34 +107,18 @@ __global__ void __launch_bounds__(kT) k_present_frame(Params P) {
     float* sz = sm + kT * 3;                  // [kT][Kp]
     if (P.use_image)
         for (uint32_t e = t; e < cnt * 3; e += kT) srgb[e] = P.image[(size_t)base * 3 + e];
-    for (uint32_t e = t; e < cnt * K; e += kT) {
-        const uint32_t row = e / K;
-        sz[row * Kp + (e - row * K)] = P.logits[(size_t)base * K + e];
-    }
+    rows_to_tile(sz, P.logits, (size_t)base * K, cnt, K, Kp, kT);
     __syncthreads();
     if (t < cnt) {
         float im[3] = {0.0f, 0.0f, 0.0f}, c[3];
         if (P.use_image) { im[0] = srgb[3 * t]; im[1] = srgb[3 * t + 1]; im[2] = srgb[3 * t + 2]; }
         if (K) {
-            float* z = sz + t * Kp;
-            float best = -1.0f, pid = 0.0f;
-            uint32_t arg = 0;
-            if (P.n_inst > 1) {
-                float mx = z[0];
-                for (uint32_t k = 1; k < K; ++k) mx = fmaxf(mx, z[k]);
-                float tr[kMaxK];
-#pragma unroll
-                for (uint32_t k = 0; k < kMaxK; ++k) tr[k] = k < K ? expf(z[k] - mx) : 0.0f;
-                const float sum = tree_sum32(tr);
-                for (uint32_t k = 0; k < K; ++k) z[k] = expf(z[k] - mx) / sum;
-            } else {
-                for (uint32_t k = 0; k < K; ++k) z[k] = 1.0f / (1.0f + expf(-z[k]));
-            }
-            for (uint32_t k = 0; k < K; ++k) {
-                const float v = z[k];
-                if (v > best) { best = v; arg = k; }           // the first index wins ties
+            float pid = 0.0f;
+            const RowBest b = instance_row<1>(sz + t * Kp, K, P.n_inst, [&](uint32_t k, float v) {
                 if ((int)k == P.id) pid = v;
-            }
+            });
+            const float best = b.best;
+            const uint32_t arg = b.arg;
             if (P.ids) P.ids[i] = (int64_t)arg;
             const float* ca = P.cmap + 3 * arg;                // arg < K <= n_colors
             const float a7 = (float)0.7, a3 = (float)(1.0 - 0.7);
@@ -173,11 +156,7 @@ __global__ void __launch_bounds__(kT) k_present_frame(Params P) {
     }
     __syncthreads();
     if (P.frame) store_pixels(P, P.frame, srgb, base, cnt, P.blend != 0);
-    if (P.probs)
-        for (uint32_t e = t; e < cnt * K; e += kT) {
-            const uint32_t row = e / K;
-            P.probs[(size_t)base * K + e] = sz[row * Kp + (e - row * K)];
-        }
+    if (P.probs) tile_to_rows(P.probs, (size_t)base * K, sz, cnt, K, Kp, kT);
 }
 
 __global__ void __launch_bounds__(kT) k_present_resize(Params P) {
@@ -197,25 +176,15 @@ __global__ void __launch_bounds__(kT) k_present_resize(Params P) {
 struct Range { float mn, mx, nan; };
 
 // min / max / any-NaN over the workgroup; every thread gets the result
-__device__ Range block_range(Range r, float* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        r.mn = fminf(r.mn, __shfl_xor(r.mn, o, 64));
-        r.mx = fmaxf(r.mx, __shfl_xor(r.mx, o, 64));
-        r.nan = fmaxf(r.nan, __shfl_xor(r.nan, o, 64));
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        float* o = sh + 3 * (threadIdx.x >> 6);
-        o[0] = r.mn; o[1] = r.mx; o[2] = r.nan;
-    }
+__device__ __forceinline__ Range block_range(Range r, float* sh) {
+    const auto op = [](uint32_t j, float a, float b) { return j == 0 ? fminf(a, b) : fmaxf(a, b); };
+    float v[3] = {r.mn, r.mx, r.nan};
+    wave_all(v, op);
+    waves_put(v, sh);
     __syncthreads();
-    Range a{sh[0], sh[1], sh[2]};
-    for (uint32_t w = 1; w < kWaves; ++w) {
-        a.mn = fminf(a.mn, sh[3 * w]);
-        a.mx = fmaxf(a.mx, sh[3 * w + 1]);
-        a.nan = fmaxf(a.nan, sh[3 * w + 2]);
-    }
-    return a;
+    float a[3] = {sh[0], sh[1], sh[2]};
+    waves_fold(a, sh, kWaves, op);
+    return Range{a[0], a[1], a[2]};
 }
 
 __global__ void __launch_bounds__(kT) k_present_minmax(Params P) {

@@ -47,6 +47,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
+from .ops import _o, _ptr, _stream
 
 MODE_R, MODE_P, MODE_C, MODE_E = 0, 1, 2, 3
 
@@ -68,18 +69,6 @@ class PhiloxBatch:
             v = getattr(self, name)
             if not (isinstance(v, int) and 0 <= v < 1 << 63):
                 raise ValueError(f"PhiloxBatch: {name} must be an integer in [0, 2^63)")
-
-
-def _o(opt, name, default):
-    return getattr(opt, name, default)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class BatchSource:

@@ -34,6 +34,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .ops import _o, _stream, torch_mask_probs
+
 HEADER_BYTES = 128
 MAX_CLASSES = 1024
 MAX_K = 64
@@ -190,7 +192,7 @@ def torch_eval_frame(pred_rgb=None, truth=None, *, bg_color=1, ssim=True, buffer
         gt_flat = gt_mask.reshape(-1)
         labeled = gt_flat != -1
         inst_mask = logits.reshape(*shape, K)
-        pred_mask = torch.softmax(inst_mask, dim=-1) if n_inst > 1 else torch.sigmoid(inst_mask)
+        pred_mask = torch_mask_probs(inst_mask, n_inst)
         flat = torch.clamp(pred_mask.reshape(-1, K), min=epsilon, max=1 - epsilon)
         if labeled.sum() > 0:
             loss = -torch.log(torch.gather(flat[labeled], -1, gt_flat[labeled][..., None]))
@@ -257,7 +259,6 @@ def read_stats(stats, n_classes=0):
 def _hip_eval_frame(pred_rgb, truth, bg_color, ssim, buffers, logits, labels, n_inst, epsilon, n_classes,
                     pred_feat, gt_feat, stats, return_extra):
     from ._lib import SamnerfEvalArgs, check, lib
-    from .ops import _stream
     ref = pred_rgb if pred_rgb is not None else (logits if logits is not None else pred_feat)
     dev = ref.device
     keep = []
@@ -357,7 +358,6 @@ def eval_confusion(pred_ids, truth_ids, n_classes=DEFAULT_CLASSES, stats=None):
     """samnerf_eval_confusion: the three histograms of two CUDA id maps into a
     stats record (returned; nothing is read back)."""
     from ._lib import check, lib
-    from .ops import _stream
     dev = pred_ids.device
     p = pred_ids.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
     t = truth_ids.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
@@ -371,10 +371,6 @@ def eval_confusion(pred_ids, truth_ids, n_classes=DEFAULT_CLASSES, stats=None):
 
 
 # ------------------------------------------------------------------ eval_step --
-
-def _o(opt, name, default):
-    return getattr(opt, name, default)
-
 
 def _field(stats, name, dtype):
     off = _HEADER.fields[name][1]

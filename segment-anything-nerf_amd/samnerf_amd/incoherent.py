@@ -39,6 +39,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, lib
+from .ops import _o, _stream, torch_mask_probs
 
 last_path = None
 # update_incoherent_mask renders as many views per render call as fit this
@@ -47,14 +48,6 @@ last_path = None
 # max_ray_batch and leaves most of the GPU idle.  The table does not depend on it.
 RAYS_PER_CALL = 1 << 18
 _INT_TYPES = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
-
-
-def _o(opt, name, default):
-    return getattr(opt, name, default)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 # ------------------------------------------------------------- torch mirror --
@@ -81,12 +74,9 @@ def torch_render_mask_ids(logits, n_inst, return_pred=False):
     update_incoherent_mask's argmax (:1767) on logits [..., K]: the ids [...]
     as uint8 (the argmax's int64 holds 0 and 1 only), and pred_mask [..., 2]
     ([..., K] at n_inst == 1) with return_pred."""
-    inst_mask = logits
+    pred_mask = torch_mask_probs(logits, n_inst)
     if n_inst > 1:
-        inst_mask = torch.softmax(inst_mask, dim=-1)
-        pred_mask = torch.stack([inst_mask[..., :-1].sum(-1), inst_mask[..., -1]], -1)
-    else:
-        pred_mask = torch.sigmoid(inst_mask)
+        pred_mask = torch.stack([pred_mask[..., :-1].sum(-1), pred_mask[..., -1]], -1)
     ids = pred_mask.argmax(-1).to(torch.uint8)
     return (ids, pred_mask) if return_pred else ids
 

@@ -23,11 +23,9 @@ import ctypes
 import torch
 import torch.nn.functional as F
 
+from .ops import _o, _ptr, _stream
+
 TERMS = ("nll", "label_regularization", "rgb_similarity", "total", "invalid")
-
-
-def _o(opt, name, default):
-    return getattr(opt, name, default)
 
 
 def rgb_similarity_active(opt, global_step):
@@ -175,7 +173,6 @@ class _HipMaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, args, keep):
         from ._lib import check, lib
-        from .ops import _ptr, _stream
         N, K = logits.shape
         dev = logits.device
         need = lib().samnerf_mask_loss_workspace_size(ctypes.byref(args))

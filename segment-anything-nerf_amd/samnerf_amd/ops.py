@@ -13,13 +13,24 @@ import torch
 from ._lib import check, lib
 
 
-def _stream(t=None):
-    dev = t.device if t is not None else None
+def _o(opt, name, default):
+    return getattr(opt, name, default)
+
+
+def _stream(where=None):
+    """The current stream of a tensor's device, of a device, or of the current device."""
+    dev = getattr(where, "device", where)
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def torch_mask_probs(logits, n_inst):
+    """The instance row of csrc/instance_row.h in torch, on logits [..., K]:
+    the softmax over the columns, or the sigmoid of a single instance."""
+    return torch.softmax(logits, dim=-1) if n_inst > 1 else torch.sigmoid(logits)
 
 
 def _cuda(t, name):

@@ -35,6 +35,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .ops import _o, _ptr, _stream, torch_mask_probs
+
 MASK_TYPES = ("heatmap", "composition", "mask")
 MODES = ("image", "depth")
 MAX_POINTS = 64
@@ -145,7 +147,7 @@ def torch_present_frame(image, depth, H, W, *, logits=None, n_inst=None, mask_ty
         if color_map is None:
             color_map = default_color_map(logits.device)
         inst_mask = logits.reshape(rH, rW, K)
-        pred_mask = torch.softmax(inst_mask, dim=-1) if n_inst > 1 else torch.sigmoid(inst_mask)
+        pred_mask = torch_mask_probs(inst_mask, n_inst)
         ids = pred_mask.argmax(-1)
         in_range = instance_id >= 0 and instance_id < n_inst
         if mask_type == "heatmap":
@@ -195,7 +197,6 @@ def torch_present_frame(image, depth, H, W, *, logits=None, n_inst=None, mask_ty
 def _hip_present_frame(image, depth, H, W, logits, n_inst, mask_type, instance_id, color_map, sam_mask, points,
                        mode, buffer, spp, return_extra):
     from ._lib import SamnerfPresentArgs, check, lib
-    from .ops import _ptr, _stream
     rH, rW, K = _shapes(image, depth, logits, n_inst)
     dev = (image if image is not None else depth).device
     keep = []
@@ -284,10 +285,6 @@ def present_frame(image, depth, H, W, *, logits=None, n_inst=None, mask_type="he
 
 
 # ------------------------------------------------------- test_step, test_gui --
-
-def _o(opt, name, default):
-    return getattr(opt, name, default)
-
 
 def _mask_kwargs(opt, outputs, color_map):
     if not _o(opt, "with_mask", False):

@@ -1,20 +1,14 @@
 """tests/golden/batch_sampler.npz (tools/make_batch_sampler_golden.py): the
 reference's get_rays and collate on a small synthetic dataset, loaded once."""
-import functools
 import json
-import os
 import types
 
-import numpy as np
 import torch
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "batch_sampler.npz")
+import golden_file
 
-
-@functools.lru_cache(maxsize=None)
-def golden():
-    with np.load(GOLDEN) as z:
-        return {k: z[k] for k in z.files}
+_G = golden_file.loader("batch_sampler.npz")
+GOLDEN, golden = _G.path, _G._file
 
 
 def tables():

@@ -4,31 +4,15 @@ evaluation, recorded; and the float64 SSIM oracle, which has no recording
 shared; arrays are handed out as fresh tensors."""
 import functools
 import json
-import os
 
 import numpy as np
 import torch
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eval.npz")
+import golden_file
+
+_G = golden_file.loader("eval.npz")
+GOLDEN, _file, arr, t, has, same = _G.path, _G._file, _G.arr, _G.t, _G.has, _G.same
 EPSILON = 0.000001
-
-
-@functools.lru_cache(maxsize=None)
-def _file():
-    with np.load(GOLDEN) as z:
-        return {k: z[k] for k in z.files}
-
-
-def arr(key):
-    return _file()[key].copy()
-
-
-def has(key):
-    return key in _file()
-
-
-def t(key):
-    return torch.from_numpy(arr(key))
 
 
 def rgb_cases():
@@ -39,13 +23,6 @@ def rgb_cases():
 def mask_cases():
     """[(index, H, W, K, n_inst, labels kind)]"""
     return [(i, *c) for i, c in enumerate(json.loads(str(_file()["mask/cases"])))]
-
-
-def same(a, b):
-    """Bit for bit, NaN equal to NaN."""
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    b = b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
 
 
 @functools.lru_cache(maxsize=None)

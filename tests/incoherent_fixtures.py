@@ -2,29 +2,16 @@
 own get_incoherent_mask and its render_mask / update_incoherent_mask lines,
 recorded.  Loaded once and shared; the arrays are handed out as fresh tensors,
 so no test changes what another reads."""
-import functools
 import json
-import os
 
 import numpy as np
 import torch
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "incoherent.npz")
+import golden_file
+
+_G = golden_file.loader("incoherent.npz")
+GOLDEN, _file, arr, t, has, same = _G.path, _G._file, _G.arr, _G.t, _G.has, _G.same
 TILE = 16                                     # SAMNERF_INCOHERENT_TILE
-
-
-@functools.lru_cache(maxsize=None)
-def _file():
-    with np.load(GOLDEN) as z:
-        return {k: z[k] for k in z.files}
-
-
-def arr(key):
-    return _file()[key].copy()
-
-
-def t(key):
-    return torch.from_numpy(arr(key))
 
 
 def mask_cases():
@@ -74,10 +61,3 @@ def update_case():
     bits = np.unpackbits(arr("update/table_packed"))[:views * S * S]
     return views, S, K, n_inst, t("update/z8").float() / 8, t("update/ids"), \
         torch.from_numpy(bits.astype(bool)).view(views, S * S)
-
-
-def same(a, b):
-    """Bit for bit, NaN equal to NaN."""
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    b = b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")

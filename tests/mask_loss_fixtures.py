@@ -1,20 +1,14 @@
 """tests/golden/mask_loss.npz (tools/make_mask_loss_golden.py: the reference's
 own Trainer.train_step on canned renders, float32 and float64) for the CPU and
 GPU tests of samnerf_amd.mask_loss, loaded once."""
-import functools
 import json
-import os
 import types
 
-import numpy as np
 import torch
 
-from conftest import GOLDEN
+import golden_file
 
-
-@functools.lru_cache(maxsize=None)
-def golden():
-    return dict(np.load(os.path.join(GOLDEN, "mask_loss.npz")))
+golden = golden_file.loader("mask_loss.npz")._file
 
 
 def case_names():

@@ -1,32 +1,16 @@
 """tests/golden/present.npz (tools/make_present_golden.py): the reference's own
 frame presentation, recorded.  Loaded once and shared; the arrays are handed
 out as fresh tensors, so no test changes what another reads."""
-import functools
 import json
-import os
 
-import numpy as np
-import torch
+import golden_file
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "present.npz")
+_G = golden_file.loader("present.npz")
+GOLDEN, _file, arr, t, has, same = _G.path, _G._file, _G.arr, _G.t, _G.has, _G.same
 MASK_TYPES = ("heatmap", "composition", "mask")
 CLICKS = ("interior", "left", "top", "right", "bottom", "corner", "all")
 SIZES = [(5, 7), (33, 65)]
 BUFFERS = [("image", "plain"), ("depth", "plain"), ("depth", "constant"), ("depth", "nan")]
-
-
-@functools.lru_cache(maxsize=None)
-def _file():
-    with np.load(GOLDEN) as z:
-        return {k: z[k] for k in z.files}
-
-
-def arr(key):
-    return _file()[key].copy()
-
-
-def t(key):
-    return torch.from_numpy(arr(key))
 
 
 def mask_cases():
@@ -50,10 +34,3 @@ def mask_views():
 
 def image_of(rH, rW):
     return t(f"image/{rH}x{rW}")
-
-
-def same(a, b):
-    """Bit for bit, NaN equal to NaN."""
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-    b = b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")

@@ -251,3 +251,22 @@ def test_eval_step_equals_the_mirror_on_the_same_render(hip_lib, cuda, monkeypat
         zero = ev.eval_step(net, dict(data, use_default_intrinsics=True), opt)[4]
         assert float(zero) == 0.0
     assert not bad, bad
+
+
+def test_second_tree_degenerates_to_the_first(hip_lib, cuda):
+    """K = 64 with columns 32 .. 63 at -inf against K = 32 on the first 32
+    columns: expf(-inf) == 0 and sum + 0 == sum, so the two-tree row gives the
+    one-tree row's bits.  11 x 29 = 319 rows: two full 128-row chunks and a
+    ragged 63 at K = 64, one full 256-row chunk and 63 at K = 32.  (Nothing
+    about nll_sum: its partials are partitioned differently at 128 and 256.)"""
+    ev = _ev()
+    H, W = 11, 29
+    z32 = 2 * torch.randn(H, W, 32, generator=torch.Generator().manual_seed(64))
+    z64 = torch.cat([z32, torch.full((H, W, 32), float("-inf"))], -1)
+    labels = (torch.arange(H * W, dtype=torch.int64) % 32).view(H, W).to(cuda)
+    a = ev.eval_frame(logits=z32.to(cuda), labels=labels, n_inst=32)
+    b = ev.eval_frame(logits=z64.to(cuda), labels=labels, n_inst=64)
+    assert b["probs"].shape == (H, W, 64)
+    assert fx.same(b["probs"][..., :32].contiguous(), a["probs"]) and fx.same(b["ids"], a["ids"])
+    assert not b["probs"][..., 32:].any()
+    assert len(set(a["ids"].view(-1).tolist())) > 1
