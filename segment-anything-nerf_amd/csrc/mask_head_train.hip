@@ -25,6 +25,8 @@
 //                run of the block's rows that share a corner row);
 //   k_mt_dw      dW0 = dz1^T x, dW1 = dz2^T h1, dW2 = g_o^T h2 over all rows: one
 //                32x32 output tile x 1,024 rows per wave, float atomics.
+// The packs, the dense layer of a workgroup's 16 rows and dW's tile decode and
+// row loop are mlp_train.h's, shared with sam_head_train.hip.
 // Rows are sample-major (row = k * N + slot), the order in which the render
 // (k_final, GEO form) leaves positions, weights and geo_feat in its workspace.
 // head_mode 1: every product is an fp32 MFMA (exact fma chains), so the
@@ -37,15 +39,13 @@
 #include <algorithm>
 
 #include "f16x3.h"
-#include "fp32_chain.h"
 #include "heads.h"
+#include "mlp_train.h"
 #include "samnerf_common.h"
 
 using namespace samnerf;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kRows = 16;                     // rows per workgroup (fwd / bwd)
 constexpr int kT = 32;                        // final samples per ray
@@ -55,10 +55,7 @@ constexpr int kOp[3] = {256, 256, 32};        // padded fan-out per layer
 #ifndef SAMNERF_MT_CHUNK
 #define SAMNERF_MT_CHUNK 1024
 #endif
-// dW's work items take the rows of a chunk in groups of 8 x kDwU (kDwU = 2
-// below): a chunk size that is not a multiple of 16 would silently drop rows
-static_assert(SAMNERF_MT_CHUNK % 16 == 0, "SAMNERF_MT_CHUNK must be a multiple of 16 (8 x kDwU)");
-constexpr uint32_t kChunk = SAMNERF_MT_CHUNK; // rows per dW work item
+constexpr uint32_t kChunk = SAMNERF_MT_CHUNK; // rows per dW work item (dw_rows: a multiple of 8 x kDwU)
 
 __host__ __device__ constexpr int pack_base(int l) {     // floats before layer l (either pack)
     int b = 0;
@@ -74,32 +71,18 @@ struct MaskW {
 __host__ __device__ inline int logical_in(int l) { return l == 0 ? kIn0 : 256; }
 __host__ __device__ inline int logical_out(int l, uint32_t K) { return l == 2 ? (int)K : 256; }
 
-// wf[l][tile t < Op/16][step s < Kp/4][lane]: A of out = W x (16x16x4):
-//   A[i = lane & 15][k = lane >> 4] = W_l[16t + i][4s + k]
-// wb[l][tile t < Kp/16][step s < Op/4][lane]: A of dx = W^T g:
-//   A[i][k] = W_l[4s + k][16t + i]
+// the two packs (mlp_train.h pack_pair) of the 3 layers
 __global__ void __launch_bounds__(256) k_mt_pack(MaskW mw, float* __restrict__ wf, float* __restrict__ wb) {
     const uint32_t e = blockIdx.x * 256u + threadIdx.x;
     if (e >= (uint32_t)kPackFloats) return;
     int l = 0;
     while (l < 2 && (int)e >= pack_base(l + 1)) ++l;
-    const uint32_t o = e - (uint32_t)pack_base(l);
-    const uint32_t lane = o & 63u, i = lane & 15u, k = lane >> 4, ts = o >> 6;
     const float* W = mw.w[l];
     const int li = logical_in(l), lo = logical_out(l, mw.K);
-    {
-        const uint32_t S = (uint32_t)kKp[l] / 4u, t = ts / S, s = ts % S;
-        const int r = (int)(16u * t + i), c = (int)(4u * s + k);
-        wf[e] = (r < lo && c < li) ? W[(size_t)r * li + c] : 0.0f;
-    }
-    {
-        const uint32_t S = (uint32_t)kOp[l] / 4u, t = ts / S, s = ts % S;
-        const int r = (int)(4u * s + k), c = (int)(16u * t + i);
-        wb[e] = (r < lo && c < li) ? W[(size_t)r * li + c] : 0.0f;
-    }
+    pack_pair(kKp[l], kOp[l], e - (uint32_t)pack_base(l), [&](int r, int c) {
+        return (r < lo && c < li) ? W[(size_t)r * li + c] : 0.0f;
+    }, wf[e], wb[e]);
 }
-
-__device__ __forceinline__ float leaky(float x) { return x >= 0.0f ? x : x * 0.01f; }
 
 struct Saved {
     float* x;      // [144][Rp]
@@ -125,28 +108,6 @@ struct FwdArgs {
     const float* wf;
     Saved sv;
 };
-
-// out[Op x 16] = W_l in[Kp x 16]: wave w owns output tiles w, w + 4, ..;
-// B operand = in[(4s + k) * 16 + j] from LDS.  Returns through `store`.
-template <int L, typename Store>
-__device__ __forceinline__ void fwd_layer(const float* __restrict__ wf, const float* in, int w, int lane,
-                                          Store store) {
-    constexpr int NT = kOp[L] / 16, MT = (NT + 3) / 4, S = kKp[L] / 4;
-    if (w >= NT) return;                                   // layer 2: waves 0, 1
-    const int j = lane & 15, k = lane >> 4;
-    f32x4 acc[MT];
-    const float* Ap[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        acc[m] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        Ap[m] = wf + pack_base(L) + (size_t)(w + 4 * m) * S * 64 + lane;
-    }
-    mfma_chain<MT, S, 4>(acc, Ap, in + k * kRows + j);
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) store(16 * (w + 4 * m) + 4 * k + r, j, acc[m][r]);
-}
 
 // the m_grid features (16 levels x 8 channels) and geo_feat of the block's 16
 // rows into X[c * 16 + j]; thread (level tid >> 4, row tid & 15)
@@ -180,19 +141,19 @@ __global__ void __launch_bounds__(256) k_mt_fwd(FwdArgs a) {
     __syncthreads();
     for (int idx = tid; idx < kKp[0] * kRows; idx += 256)
         sv.x[(size_t)(idx / kRows) * sv.Rp + r0 + (idx % kRows)] = X[idx];
-    fwd_layer<0>(a.wf, X, w, lane, [&](int u, int j, float z) {
+    dense16<kKp[0] / 4, kOp[0] / 16>(a.wf + pack_base(0), X, w, lane, [&](int u, int j, float z) {
         const float h = r0 + (uint32_t)j < sv.R ? leaky(z) : 0.0f;
         H1[u * kRows + j] = h;
         sv.h1[(size_t)u * sv.Rp + r0 + j] = h;
     });
     __syncthreads();
-    fwd_layer<1>(a.wf, H1, w, lane, [&](int u, int j, float z) {
+    dense16<kKp[1] / 4, kOp[1] / 16>(a.wf + pack_base(1), H1, w, lane, [&](int u, int j, float z) {
         const float h = r0 + (uint32_t)j < sv.R ? leaky(z) : 0.0f;
         H2[u * kRows + j] = h;
         sv.h2[(size_t)u * sv.Rp + r0 + j] = h;
     });
     __syncthreads();
-    fwd_layer<2>(a.wf, H2, w, lane, [&](int u, int j, float z) {
+    dense16<kKp[2] / 4, kOp[2] / 16>(a.wf + pack_base(2), H2, w, lane, [&](int u, int j, float z) {
         sv.o[(size_t)u * sv.Rp + r0 + j] = r0 + (uint32_t)j < sv.R ? z : 0.0f;
     });
 }
@@ -242,31 +203,6 @@ __global__ void __launch_bounds__(256) k_mt_rep_sum(const float* __restrict__ re
 #pragma unroll
     for (uint32_t c = 0; c < kRep; ++c) acc += rep[(size_t)c * n + i];
     gemb[i] += acc;
-}
-
-// dx[Kp x 16] = W_l^T g[Op x 16]: output tiles t = w, w + 4, .. of NT (tiles
-// past NT repeat the last and are dropped: the chain stays branch-free)
-template <int L, int NT, typename Store>
-__device__ __forceinline__ void bwd_layer(const float* __restrict__ wb, const float* g, int w, int lane,
-                                          Store store) {
-    constexpr int MT = (NT + 3) / 4, S = kOp[L] / 4;
-    const int j = lane & 15, k = lane >> 4;
-    f32x4 acc[MT];
-    const float* Ap[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        acc[m] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        const int t = min(w + 4 * m, NT - 1);
-        Ap[m] = wb + pack_base(L) + (size_t)t * S * 64 + lane;
-    }
-    mfma_chain<MT, S, 4>(acc, Ap, g + k * kRows + j);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const int t = w + 4 * m;
-        if (t >= NT) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) store(16 * t + 4 * k + r, j, acc[m][r]);
-    }
 }
 
 // the trilinear scatter of dx's m_grid part (Q [128][16] of the block's rows)
@@ -331,25 +267,26 @@ __global__ void __launch_bounds__(256) k_mt_bwd(BwdArgs a) {
         sv.go[(size_t)u * sv.Rp + r] = g;
     }
     __syncthreads();
-    // torch's leaky_relu backward: grad * (result > 0 ? 1 : slope)
-    bwd_layer<2, 16>(a.wb, P, w, lane, [&](int v, int j, float d) {
+    // dx = W_l^T g (wb pack, Kp_l / 16 output tiles over Op_l / 4 k-steps)
+    dense16<kOp[2] / 4, kKp[2] / 16>(a.wb + pack_base(2), P, w, lane, [&](int v, int j, float d) {
         const uint32_t r = r0 + (uint32_t)j;
         const float h = sv.h2[(size_t)v * sv.Rp + r];
-        const float gz = r < sv.R ? (h > 0.0f ? d : d * 0.01f) : 0.0f;
+        const float gz = r < sv.R ? leaky_grad(h, d) : 0.0f;
         Q[v * kRows + j] = gz;
         sv.g2[(size_t)v * sv.Rp + r] = gz;
     });
     __syncthreads();
-    bwd_layer<1, 16>(a.wb, Q, w, lane, [&](int v, int j, float d) {
+    dense16<kOp[1] / 4, kKp[1] / 16>(a.wb + pack_base(1), Q, w, lane, [&](int v, int j, float d) {
         const uint32_t r = r0 + (uint32_t)j;
         const float h = sv.h1[(size_t)v * sv.Rp + r];
-        const float gz = r < sv.R ? (h > 0.0f ? d : d * 0.01f) : 0.0f;
+        const float gz = r < sv.R ? leaky_grad(h, d) : 0.0f;
         P[v * kRows + j] = gz;
         sv.g1[(size_t)v * sv.Rp + r] = gz;
     });
     __syncthreads();
     // dx of the m_grid part (tiles 0..7 of 9; geo_feat is detached) into Q
-    bwd_layer<0, 8>(a.wb, P, w, lane, [&](int v, int j, float d) { Q[v * kRows + j] = d; });
+    dense16<kOp[0] / 4, 8>(a.wb + pack_base(0), P, w, lane,
+                           [&](int v, int j, float d) { Q[v * kRows + j] = d; });
     __syncthreads();
     mt_scatter(a, sLv, Q, r0, w, lane);
 }
@@ -542,80 +479,40 @@ struct DwArgs {
     float* gw[3];            // [256][143] [256][256] [K][256], zeroed, accumulated
 };
 
-constexpr int kDwTilesK[3] = {5, 8, 8};                  // 32-wide input tiles per layer
-constexpr int kDwTilesU[3] = {8, 8, 1};                  // 32-wide output tiles per layer
-__host__ __device__ constexpr int dw_items_before(int l) {
-    int b = 0;
-    for (int i = 0; i < l; ++i) b += kDwTilesU[i] * kDwTilesK[i];
-    return b;
-}
-constexpr int kDwTiles = dw_items_before(3);             // 112 output tiles of 32 x 32
+constexpr DwTiles<3> kDw = {{8, 8, 1}, {5, 8, 8}};       // 32-wide tiles of Op_l units x Kp_l inputs
+constexpr int kDwTiles = kDw.total();                    // 112 output tiles of 32 x 32
 
 // dW_l[u][c] += sum over a chunk of rows of G_l[u][r] X_l[c][r] (G: dz1 / dz2
-// / g_o, X: x / h1 / h2); one wave per (output tile, chunk).  The rows of an
-// MFMA's k pair can be any two: lane half h of group m takes rows
-// c0 + 8m + 4h .. +3 over four MFMAs, one 16-B load per operand.
+// / g_o, X: x / h1 / h2); one wave per (output tile, chunk), the rows through
+// mlp_train.h's dw_rows, the finished tile added with float atomics.
 __global__ void __launch_bounds__(256) k_mt_dw(DwArgs a) {
     const uint32_t item = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t chunks = a.sv.Rp / kChunk;
     if (item >= (uint32_t)kDwTiles * chunks) return;
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     const uint32_t tile = item % kDwTiles, chunk = item / kDwTiles;
-    int l = 0;
-    while (l < 2 && (int)tile >= dw_items_before(l + 1)) ++l;
-    const int lt = (int)tile - dw_items_before(l);
-    const int ut = lt / kDwTilesK[l], kt = lt % kDwTilesK[l];
+    const DwItem it = dw_item(kDw, (int)tile);
+    const int l = it.l;
     const uint32_t c0 = chunk * kChunk;
-    const int u = 32 * ut + i, c = 32 * kt + i;              // A row (unit) / B column (input)
+    const int u = 32 * it.ut + i, c = 32 * it.kt + i;        // A row (unit) / B column (input)
     const Saved& sv = a.sv;
     const float* G = l == 0 ? sv.g1 : l == 1 ? sv.g2 : sv.go;
     const float* X = l == 0 ? sv.x : l == 1 ? sv.h1 : sv.h2;
-    const bool gok = u < kOp[l], xok = c < kKp[l];
-    const float* Ga = G + (size_t)(gok ? u : 0) * sv.Rp + c0 + 4 * h;
-    const float* Xb = X + (size_t)(xok ? c : 0) * sv.Rp + c0 + 4 * h;
+    // every u is a saved row (the unit tiles cover Op_l exactly); the columns
+    // past Kp_l (layer 0: 144 .. 159) read row 0 instead and are dropped below
+    // with the rest past the logical fan-in: a column's X values reach no
+    // other column of the tile
+    const float* Ga = G + (size_t)u * sv.Rp + c0 + 4 * h;
+    const float* Xb = X + (size_t)(c < kKp[l] ? c : 0) * sv.Rp + c0 + 4 * h;
     f32x16 acc = {};
-    // the rows in groups of kDwU loop trips, two register buffers in ping-pong
-    // (fp32_chain.h's scheme): a group's loads are in flight while the
-    // previous group's MFMAs run, where one load pair then its four MFMAs
-    // waited for L2 on every trip.  The MFMA order is unchanged.
-    constexpr int kDwU = 2, kDwG = (int)(kChunk / 8u) / kDwU;
-    const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    auto load = [&](float4 (&ga)[kDwU], float4 (&xb)[kDwU], int grp) {
-#pragma unroll
-        for (int u = 0; u < kDwU; ++u) {
-            const int m = grp * kDwU + u;
-            ga[u] = *reinterpret_cast<const float4*>(Ga + 8 * m);   // rows clamped in range:
-            xb[u] = *reinterpret_cast<const float4*>(Xb + 8 * m);   // unconditional loads
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto mma = [&](const float4 (&ga)[kDwU], const float4 (&xb)[kDwU]) {
-#pragma unroll
-        for (int u = 0; u < kDwU; ++u) {
-            const float4 g = gok ? ga[u] : zero4, x = xok ? xb[u] : zero4;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g.x, x.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g.y, x.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g.z, x.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g.w, x.w, acc, 0, 0, 0);
-        }
-    };
-    float4 g0[kDwU], x0[kDwU], g1[kDwU], x1[kDwU];
-    load(g0, x0, 0);
-#pragma unroll 1
-    for (int grp = 0; grp < kDwG; grp += 2) {
-        load(g1, x1, min(grp + 1, kDwG - 1));
-        mma(g0, x0);
-        if (grp + 1 < kDwG) {
-            load(g0, x0, min(grp + 2, kDwG - 1));
-            mma(g1, x1);
-        }
-    }
-    // acc register q of lane (col i, half h) = dW[32ut + (q & 3) + 8 (q >> 2) + 4h][32kt + i]
+    dw_rows<kChunk>(
+        acc, [&](int m) { return *reinterpret_cast<const float4*>(Ga + 8 * m); },
+        [&](int m) { return *reinterpret_cast<const float4*>(Xb + 8 * m); });
     const int lo = logical_out(l, a.K), li = logical_in(l);
     if (c >= li) return;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int row = 32 * ut + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int row = 32 * it.ut + dw_row(q, h);
         if (row < lo) atomicAdd(a.gw[l] + (size_t)row * li + c, acc[q]);
     }
 }
@@ -630,34 +527,26 @@ struct Layout {
     size_t bytes;
 };
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 Layout carve(uint32_t N, void* base) {
     Layout L{};
     const uint32_t R = N * (uint32_t)kT;
     L.sv.R = R;
     L.sv.Rp = (R + kChunk - 1u) / kChunk * kChunk;
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* q = base ? reinterpret_cast<float*>(p + off) : nullptr;
-        off += al256(floats * sizeof(float));
-        return q;
-    };
+    Carver c(base);
     const size_t Rp = L.sv.Rp;
-    L.wf = take(kPackFloats);
-    L.wb = take(kPackFloats);
-    L.pk16 = reinterpret_cast<uint4*>(take((size_t)kPack16Vec * 4u));
-    L.kexp16 = reinterpret_cast<int*>(take(4 + 3 * kW16Parts));
-    L.rep = take((size_t)kRep * kRepRows * 8u);
-    L.sv.x = take((size_t)kKp[0] * Rp);
-    L.sv.h1 = take((size_t)256 * Rp);
-    L.sv.h2 = take((size_t)256 * Rp);
-    L.sv.o = take((size_t)32 * Rp);
-    L.sv.go = take((size_t)32 * Rp);
-    L.sv.g2 = take((size_t)256 * Rp);
-    L.sv.g1 = take((size_t)256 * Rp);
-    L.bytes = off;
+    L.wf = c.take(kPackFloats);
+    L.wb = c.take(kPackFloats);
+    L.pk16 = c.take<uint4>((size_t)kPack16Vec * 4u);
+    L.kexp16 = c.take<int>(4 + 3 * kW16Parts);
+    L.rep = c.take((size_t)kRep * kRepRows * 8u);
+    L.sv.x = c.take((size_t)kKp[0] * Rp);
+    L.sv.h1 = c.take((size_t)256 * Rp);
+    L.sv.h2 = c.take((size_t)256 * Rp);
+    L.sv.o = c.take((size_t)32 * Rp);
+    L.sv.go = c.take((size_t)32 * Rp);
+    L.sv.g2 = c.take((size_t)256 * Rp);
+    L.sv.g1 = c.take((size_t)256 * Rp);
+    L.bytes = c.bytes();
     return L;
 }
 

@@ -146,7 +146,6 @@ k_composite(const float* __restrict__ rb, const float* __restrict__ sig, uint32_
 
 namespace {
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 thread_local hipEvent_t g_stage_events[8];
 thread_local uint32_t g_n_stage_events = 0;
@@ -210,42 +209,36 @@ bool box4_ok(const GridDesc<16>& g) {
 
 Workspace carve(const samnerf_model* m, uint32_t N, void* base) {
     Workspace w;
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* q = base ? reinterpret_cast<float*>(p + off) : nullptr;
-        off += align256(floats * sizeof(float));
-        return q;
-    };
+    Carver c(base);
     const size_t n = N;
     // the packed weights first: their offsets do not depend on N, so a
     // render of another ray count on the same workspace finds them where
     // the packing render left them (samnerf_model::reuse_packed)
-    w.gpack = reinterpret_cast<uint4*>(take((size_t)2 * kFSlots * 64 * 4));
-    w.gexp = reinterpret_cast<int*>(take(4));
-    w.packed = take(m->with_sam ? sam_head_packed_floats() : 0);
-    w.snf = take(2 * n);
-    w.rec = reinterpret_cast<float4*>(take(8 * n));
-    w.bins1 = take((m->num_steps[1] + 1) * n);
-    w.bins2 = take((m->num_steps[2] + 1) * n);
-    w.wtmp = take((size_t)std::max(m->num_steps[0], m->num_steps[1]) * n);
-    w.u_f = take(3 * (size_t)m->num_steps[2] * n);
-    w.w_f = take((size_t)m->num_steps[2] * n);
-    w.rows = take((size_t)kRow * n);
+    w.gpack = c.take<uint4>((size_t)2 * kFSlots * 64 * 4);
+    w.gexp = c.take<int>(4);
+    w.packed = c.take(m->with_sam ? sam_head_packed_floats() : 0);
+    w.snf = c.take(2 * n);
+    w.rec = c.take<float4>(8 * n);
+    w.bins1 = c.take((m->num_steps[1] + 1) * n);
+    w.bins2 = c.take((m->num_steps[2] + 1) * n);
+    w.wtmp = c.take((size_t)std::max(m->num_steps[0], m->num_steps[1]) * n);
+    w.u_f = c.take(3 * (size_t)m->num_steps[2] * n);
+    w.w_f = c.take((size_t)m->num_steps[2] * n);
+    w.rows = c.take((size_t)kRow * n);
     const bool mdef = m->with_mask && m->mask_kind == 0, madapt = m->with_mask && m->mask_kind > 0;
-    w.geo_f = take(mdef ? (size_t)16 * m->num_steps[2] * n : 0);
-    w.mpacked = take(mdef ? mask_head_packed_floats() : 0);
-    w.aeff = take(madapt ? (size_t)32 * kAeff : 0);
-    w.mlog = take(madapt ? (size_t)m->mask_out * n : 0);
-    w.xsum = take(madapt && m->with_mask == 2 ? (size_t)kAeff * n : 0);   // training renders only
+    w.geo_f = c.take(mdef ? (size_t)16 * m->num_steps[2] * n : 0);
+    w.mpacked = c.take(mdef ? mask_head_packed_floats() : 0);
+    w.aeff = c.take(madapt ? (size_t)32 * kAeff : 0);
+    w.mlog = c.take(madapt ? (size_t)m->mask_out * n : 0);
+    w.xsum = c.take(madapt && m->with_mask == 2 ? (size_t)kAeff * n : 0);   // training renders only
     const bool n1 = m->t_thresh > 0.0f;
-    w.n1_list = reinterpret_cast<uint32_t*>(take(n1 ? 2 * n : 0));
-    w.n1_cnt = reinterpret_cast<uint32_t*>(take(n1 ? 2 : 0));
-    w.n1_mask = reinterpret_cast<uint64_t*>(take(n1 ? 2 * ((n + 31) / 32) : 0));
-    w.n1_base = reinterpret_cast<uint32_t*>(take(n1 ? (n + 31) / 32 : 0));
-    w.n1_std = reinterpret_cast<double*>(take(n1 ? 6 * n : 0));
-    w.n1_stf = take(n1 ? 16 * n : 0);
-    w.bytes = off;
+    w.n1_list = c.take<uint32_t>(n1 ? 2 * n : 0);
+    w.n1_cnt = c.take<uint32_t>(n1 ? 2 : 0);
+    w.n1_mask = c.take<uint64_t>(n1 ? 2 * ((n + 31) / 32) : 0);
+    w.n1_base = c.take<uint32_t>(n1 ? (n + 31) / 32 : 0);
+    w.n1_std = c.take<double>(n1 ? 6 * n : 0);
+    w.n1_stf = c.take(n1 ? 16 * n : 0);
+    w.bytes = c.bytes();
     return w;
 }
 

@@ -1101,35 +1101,29 @@ void rep_span(const int32_t* offsets, int levels, uint32_t& n_levels, uint32_t& 
 
 RtWorkspace carve_rt(const samnerf_model* m, uint32_t N, void* base) {
     RtWorkspace w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* q = base ? reinterpret_cast<float*>(p + off) : nullptr;
-        off += (floats * sizeof(float) + 255) & ~(size_t)255;
-        return q;
-    };
+    Carver c(base);
     const size_t n = N;
-    w.p.snf = take(2 * n);
-    w.p.rec = reinterpret_cast<float4*>(take(8 * n));
-    w.p.ds0 = take(128 * n);
-    w.p.w0 = take(128 * n);
-    w.p.bins1 = take(65 * n);
-    w.p.ds1 = take(64 * n);
-    w.p.w1 = take(64 * n);
-    w.p.bins2 = take(33 * n);
-    w.dds0 = take(128 * n);
-    w.dds1 = take(64 * n);
-    for (int i = 0; i < 10; ++i) w.fin[i] = take((size_t)kFinCh[i] * kT * n);
-    for (int i = 0; i < 10; ++i) w.ray[i] = take((size_t)kRayCh[i] * n);
+    w.p.snf = c.take(2 * n);
+    w.p.rec = c.take<float4>(8 * n);
+    w.p.ds0 = c.take(128 * n);
+    w.p.w0 = c.take(128 * n);
+    w.p.bins1 = c.take(65 * n);
+    w.p.ds1 = c.take(64 * n);
+    w.p.w1 = c.take(64 * n);
+    w.p.bins2 = c.take(33 * n);
+    w.dds0 = c.take(128 * n);
+    w.dds1 = c.take(64 * n);
+    for (int i = 0; i < 10; ++i) w.fin[i] = c.take((size_t)kFinCh[i] * kT * n);
+    for (int i = 0; i < 10; ++i) w.ray[i] = c.take((size_t)kRayCh[i] * n);
     // the largest slab: grid_mlp.1 (64 x 64) over 32 N samples, or a proposal
     // MLP (16 x 10) over 128 N
     const size_t sf = (size_t)kT * n, sp = (size_t)128 * n;
     const size_t sb = std::max((size_t)div_up(sf, outer_chunk(sf)) * 4096, (size_t)div_up(sp, 256) * kPropW);
-    w.slab = take(sb);
+    w.slab = c.take(sb);
     rep_span(m->grid.offsets_host, 16, w.rep_levels[0], w.rep_floats[0]);
     for (int p = 0; p < 2; ++p) rep_span(m->prop[p].offsets_host, 5, w.rep_levels[1 + p], w.rep_floats[1 + p]);
-    w.rep = take((size_t)kRep * std::max(w.rep_floats[0], std::max(w.rep_floats[1], w.rep_floats[2])));
-    w.bytes = off;
+    w.rep = c.take((size_t)kRep * std::max(w.rep_floats[0], std::max(w.rep_floats[1], w.rep_floats[2])));
+    w.bytes = c.bytes();
     return w;
 }
 

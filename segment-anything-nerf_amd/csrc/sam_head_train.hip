@@ -27,17 +27,19 @@
 // (an fma chain in k order, cdna_hip_programming.md "FP32-input MFMA"), so
 // the gradients match torch's fp32 autograd to summation-order rounding.
 // 16 rays per workgroup: 256 workgroups for a 4,096-ray step fill the chip.
+// The scheme -- the packs, the dense layer of a workgroup's 16 rays, the dW
+// tile decode and 8-row MFMA group -- is mlp_train.h's, shared with
+// mask_head_train.hip; here are the layers' epilogues (bias, leaky_relu, the
+// skip rows), LayerNorm, and the ordered sums of the dW tiles.
 #include <algorithm>
 #include <cstring>
 
-#include "fp32_chain.h"
+#include "mlp_train.h"
 #include "samnerf_common.h"
 
 using namespace samnerf;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kIn = 163;            // head inputs (f_sam 128, f_image 31, image 3, depth 1)
 constexpr int kRowIn = 164;         // row stride of the render's head-input rows
@@ -64,34 +66,19 @@ struct HeadW {
     const float* ln_b;
 };
 
-// Wf[l][tile t 0..15][step s 0..Kp/4-1][lane]: A of out = W x, 16x16x4:
-//   A[i = lane & 15][k = lane >> 4] = W_l[16t + i][4s + k]
-// Wb[l][tile t 0..Kp/16-1][step s 0..63][lane]: A of dX = W^T G:
-//   A[i][k] = W_l[4s + k][16t + i]
+// the two packs (mlp_train.h pack_pair) of the 5 layers, Op = 256
 __global__ void __launch_bounds__(256) k_ht_pack(HeadW hw, float* __restrict__ wf, float* __restrict__ wb) {
     const uint32_t e = blockIdx.x * 256u + threadIdx.x;
     if (e >= (uint32_t)kPackFloats) return;
     int l = 0;
     while (l < 4 && (int)e >= fwd_base(l + 1)) ++l;
-    const uint32_t o = e - (uint32_t)fwd_base(l);
-    const uint32_t lane = o & 63u, i = lane & 15u, k = lane >> 4;
     const float* W = hw.w[l];
     const int kl = kKl[l];
-    {   // forward: o = (t * Kp/4 + s) * 64 + lane
-        const uint32_t ts = o >> 6, S = (uint32_t)kKp[l] / 4u;
-        const uint32_t t = ts / S, s = ts % S;
-        const int col = kcol(l, (int)(4u * s + k));
-        wf[e] = col >= 0 ? W[(size_t)(16u * t + i) * kl + col] : 0.0f;
-    }
-    {   // transposed: o = (t * 64 + s) * 64 + lane
-        const uint32_t ts = o >> 6;
-        const uint32_t t = ts >> 6, s = ts & 63u;
-        const int col = kcol(l, (int)(16u * t + i));
-        wb[e] = col >= 0 ? W[(size_t)(4u * s + k) * kl + col] : 0.0f;
-    }
+    pack_pair(kKp[l], 256, e - (uint32_t)fwd_base(l), [&](int r, int c) {
+        const int col = kcol(l, c);
+        return col >= 0 ? W[(size_t)r * kl + col] : 0.0f;
+    }, wf[e], wb[e]);
 }
-
-__device__ __forceinline__ float leaky(float x) { return x >= 0.0f ? x : x * 0.01f; }
 
 struct FwdArgs {
     HeadW hw;
@@ -102,34 +89,6 @@ struct FwdArgs {
     float* hsave;          // [5][256][Np]: h0..h3 (post leaky_relu), y (pre LayerNorm)
     float* stats;          // [Np][2]: mean, rstd
 };
-
-// out[256 x 16] = act(W_l in[Kp x 16] + b): wave w owns the output tiles
-// 4w..4w+3 (units 64w..64w+63); B operand = in[(4s + k) * 16 + j] from LDS.
-template <int L>
-__device__ __forceinline__ void fwd_layer(const FwdArgs& a, const float* in, float* out, int w, int lane,
-                                          uint32_t ray0) {
-    constexpr int S = kKp[L] / 4;
-    const int j = lane & 15, k = lane >> 4;
-    f32x4 acc[4];
-    const float* Ap[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        acc[t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        Ap[t] = a.wf + fwd_base(L) + (size_t)(4 * w + t) * S * 64 + lane;
-    }
-    mfma_chain<4, S, 4>(acc, Ap, in + k * kRays + j);
-    const bool live = ray0 + (uint32_t)j < a.N;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int u = 16 * (4 * w + t) + 4 * k + r;
-            const float z = acc[t][r] + a.hw.b[L][u];
-            const float h = L < 4 ? leaky(z) : z;
-            out[u * kRays + j] = h;
-            a.hsave[((size_t)L * 256 + u) * a.Np + ray0 + j] = live ? h : 0.0f;
-        }
-}
 
 __global__ void __launch_bounds__(256) k_ht_fwd(FwdArgs a) {
     __shared__ float P[256 * kRays];
@@ -144,15 +103,28 @@ __global__ void __launch_bounds__(256) k_ht_fwd(FwdArgs a) {
         Q[(256 + c) * kRays + jr] = (c < kIn && ray < a.N) ? a.rows[(size_t)ray * kRowIn + c] : 0.0f;
     }
     __syncthreads();
-    fwd_layer<0>(a, Q + 256 * kRays, P, w, lane, ray0);
+    // layer l's epilogue: h = act(z + b_l) into out (LDS) and saved for the backward
+    auto act = [&](int l, float* out) {
+        return [=, &a](int u, int j, float z) {
+            z += a.hw.b[l][u];
+            const float h = l < 4 ? leaky(z) : z;
+            out[u * kRays + j] = h;
+            a.hsave[((size_t)l * 256 + u) * a.Np + ray0 + j] = ray0 + (uint32_t)j < a.N ? h : 0.0f;
+        };
+    };
+    // wave w keeps the adjacent tiles 4w .. 4w + 3 (units 64w .. 64w + 63):
+    // in dense16's w, w + 4, .. order this kernel measured 54.7 against 53.4 us
+    // (4,096 rays, three alternating profiler passes, the parent's spread 0.4)
+    constexpr bool kAdj = true;
+    dense16<kKp[0] / 4, 16, kRays, kAdj>(a.wf + fwd_base(0), Q + 256 * kRays, w, lane, act(0, P));
     __syncthreads();
-    fwd_layer<1>(a, P, Q, w, lane, ray0);
+    dense16<kKp[1] / 4, 16, kRays, kAdj>(a.wf + fwd_base(1), P, w, lane, act(1, Q));
     __syncthreads();
-    fwd_layer<2>(a, Q, P, w, lane, ray0);
+    dense16<kKp[2] / 4, 16, kRays, kAdj>(a.wf + fwd_base(2), Q, w, lane, act(2, P));
     __syncthreads();
-    fwd_layer<3>(a, P, Q, w, lane, ray0);
+    dense16<kKp[3] / 4, 16, kRays, kAdj>(a.wf + fwd_base(3), P, w, lane, act(3, Q));
     __syncthreads();
-    fwd_layer<4>(a, Q, P, w, lane, ray0);
+    dense16<kKp[4] / 4, 16, kRays, kAdj>(a.wf + fwd_base(4), Q, w, lane, act(4, P));
     __syncthreads();
     // LayerNorm(256, eps 1e-5) per ray over P[u][ray]: two passes
     const int j = tid & 15, p = tid >> 4;
@@ -217,55 +189,6 @@ __device__ __forceinline__ void zero_grads(const BwdArgs& a) {
         for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < a.zero_n[t]; e += stride) a.zero[t][e] = 0.0f;
 }
 
-// dX[Kp x 16] = W_l^T G[256 x 16]: output tiles t = w, w + 4, .. of Kp/16.
-// MODE 0: the next G = dX * leaky'(h_{l-1}) into out (+ save for k_ht_dw)
-// MODE 1 (layer 2): rows < 256 as MODE 0, rows >= 256 raw into out (skip)
-// MODE 2 (layer 0): grows = dX + skip (out holds the skip rows at 256 + c)
-template <int L, int MODE>
-__device__ __forceinline__ void bwd_layer(const BwdArgs& a, const float* in, float* out, int w, int lane,
-                                          uint32_t ray0) {
-    constexpr int NT = kKp[L] / 16;
-    constexpr int MT = (NT + 3) / 4;
-    const int j = lane & 15, k = lane >> 4;
-    const uint32_t ray = ray0 + (uint32_t)j;
-    const bool live = ray < a.N;
-    f32x4 acc[MT];
-    const float* Ap[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        acc[m] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        // tiles past NT (layers 0 and 2: 11 and 27 tiles over 4 waves) repeat
-        // the last tile and are dropped below: the chain stays branch-free
-        const int t = min(w + 4 * m, NT - 1);
-        Ap[m] = a.wb + fwd_base(L) + (size_t)t * 64 * 64 + lane;
-    }
-    mfma_chain<MT, 64, 4>(acc, Ap, in + k * kRays + j);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const int t = w + 4 * m;
-        if (t >= NT) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int v = 16 * t + 4 * k + r;               // input unit of layer L
-            const float dx = acc[m][r];
-            if (MODE == 2) {
-                if (v < kIn && live) a.grows[(size_t)ray * kRowIn + v] = dx + out[(256 + v) * kRays + j];
-                if (v == kIn && live) a.grows[(size_t)ray * kRowIn + v] = 0.0f;
-                continue;
-            }
-            if (MODE == 1 && v >= 256) {                    // d / d x through the skip
-                out[v * kRays + j] = dx;
-                continue;
-            }
-            // torch's in-place leaky_relu backward: grad * (result > 0 ? 1 : slope)
-            const float h = a.hsave[((size_t)(L - 1) * 256 + v) * a.Np + ray];
-            const float gz = live ? (h > 0.0f ? dx : dx * 0.01f) : 0.0f;
-            out[v * kRays + j] = gz;
-            a.G[((size_t)(L - 1) * 256 + v) * a.Np + ray] = gz;
-        }
-    }
-}
-
 __global__ void __launch_bounds__(256) k_ht_bwd(BwdArgs a) {
     __shared__ float P[256 * kRays];
     __shared__ float Q[432 * kRays];
@@ -319,15 +242,35 @@ __global__ void __launch_bounds__(256) k_ht_bwd(BwdArgs a) {
         }
     }
     __syncthreads();
-    bwd_layer<4, 0>(a, P, Q, w, lane, ray0);      // -> G3
+    // dX = W_l^T G_l (wb pack, Kp_l / 16 output tiles over 64 k-steps), then
+    // G_{l-1} = dX * leaky'(h_{l-1}) into out (LDS) and saved for k_ht_dw
+    auto to_g = [&](int l, float* out) {
+        return [=, &a](int v, int j, float dx) {
+            const uint32_t ray = ray0 + (uint32_t)j;
+            const float h = a.hsave[((size_t)(l - 1) * 256 + v) * a.Np + ray];
+            const float gz = ray < a.N ? leaky_grad(h, dx) : 0.0f;
+            out[v * kRays + j] = gz;
+            a.G[((size_t)(l - 1) * 256 + v) * a.Np + ray] = gz;
+        };
+    };
+    dense16<64, kKp[4] / 16>(a.wb + fwd_base(4), P, w, lane, to_g(4, Q));      // -> G3
     __syncthreads();
-    bwd_layer<3, 0>(a, Q, P, w, lane, ray0);      // -> G2
+    dense16<64, kKp[3] / 16>(a.wb + fwd_base(3), Q, w, lane, to_g(3, P));      // -> G2
     __syncthreads();
-    bwd_layer<2, 1>(a, P, Q, w, lane, ray0);      // -> G1 (rows < 256) + skip d x (rows 256..431)
+    // layer 2: rows < 256 -> G1; rows 256..431, d / d x through the skip, raw into Q
+    dense16<64, kKp[2] / 16>(a.wb + fwd_base(2), P, w, lane, [&](int v, int j, float dx) {
+        if (v >= 256) Q[v * kRays + j] = dx;
+        else to_g(2, Q)(v, j, dx);
+    });
     __syncthreads();
-    bwd_layer<1, 0>(a, Q, P, w, lane, ray0);      // -> G0
+    dense16<64, kKp[1] / 16>(a.wb + fwd_base(1), Q, w, lane, to_g(1, P));      // -> G0
     __syncthreads();
-    bwd_layer<0, 2>(a, P, Q, w, lane, ray0);      // -> d rows = W0^T G0 + skip
+    // layer 0: d rows = W0^T G0 + skip (Q rows 256 + v), column 163 written 0
+    dense16<64, kKp[0] / 16>(a.wb + fwd_base(0), P, w, lane, [&](int v, int j, float dx) {
+        const uint32_t ray = ray0 + (uint32_t)j;
+        if (v > kIn || ray >= a.N) return;
+        a.grows[(size_t)ray * kRowIn + v] = v < kIn ? dx + Q[(256 + v) * kRays + j] : 0.0f;
+    });
 }
 
 struct DwArgs {
@@ -345,24 +288,18 @@ struct DwArgs {
     float* gln_b;
 };
 
-constexpr int kDwTilesK[5] = {6, 8, 14, 8, 8};          // 32-wide column tiles of Kp_l
-__host__ __device__ constexpr int dw_items_before(int l) {
-    int b = 0;
-    for (int i = 0; i < l; ++i) b += 8 * kDwTilesK[i];
-    return b;
-}
-constexpr int kDwTiles = dw_items_before(5);              // 352 output tiles of 32 x 32
+constexpr DwTiles<5> kDw = {{8, 8, 8, 8, 8}, {6, 8, 14, 8, 8}};   // 32-wide tiles of 256 units x Kp_l
+constexpr int kDwTiles = kDw.total();                     // 352 output tiles of 32 x 32
 
 // dW_l[u][k] = sum over the rays of G_l[u][r] X_l[k][r], in a FIXED order
 // (round 5: the gradients of a step repeat bit for bit -- the round-2..4 form
 // added each 256-ray chunk's tile with float atomics, in whatever order the
 // waves finished).  One wave per (output tile, part): part p sums chunks p,
 // p + parts, .. in order into its accumulators and stores the tile to the
-// slab; k_ht_dw_sum adds the parts in order.  The sum runs over rays, so the
-// rays of an MFMA's k pair can be any two: lane half h of group m takes rays
-// c0 + 8m + 4h .. +3 over four MFMAs, one 16-B load per operand.  The waves
-// of the first column tile (kt 0) also sum their G rows: the bias gradient.
-// After the tiles, 8 waves per part sum the part's LN partials.
+// slab; k_ht_dw_sum adds the parts in order.  Tiles and rows as mlp_train.h
+// lays them out (dw_item, dw_mma, dw_row).  The waves of the first column
+// tile (kt 0) also sum their G rows: the bias gradient.  After the tiles, 8
+// waves per part sum the part's LN partials.
 constexpr uint32_t kDwParts = 16;
 constexpr size_t kDwSlabTile = (size_t)kDwTiles * 1024;   // floats per part: the weight tiles
 __host__ __device__ constexpr size_t dw_slab_floats(uint32_t parts) {
@@ -387,11 +324,9 @@ __global__ void __launch_bounds__(256) k_ht_dw(DwArgs a) {
         return;
     }
     const uint32_t tile = item % kDwTiles, part = item / kDwTiles;
-    int l = 0;
-    while (l < 4 && (int)tile >= dw_items_before(l + 1)) ++l;
-    const int lt = (int)tile - dw_items_before(l);
-    const int ut = lt / kDwTilesK[l], kt = lt % kDwTilesK[l];
-    const int u = 32 * ut + i, kk = 32 * kt + i;           // A row (unit) / B column (input) of this lane
+    const DwItem it = dw_item(kDw, (int)tile);
+    const int l = it.l, kt = it.kt;
+    const int u = 32 * it.ut + i, kk = 32 * kt + i;        // A row (unit) / B column (input) of this lane
     // B source: saved activations (unit-major, ray-contiguous) or the rows
     const bool from_x = (l == 0) || (l == 2 && kk >= 256);
     const int xc = l == 0 ? kk : kk - 256;                  // x column for from_x
@@ -403,34 +338,35 @@ __global__ void __launch_bounds__(256) k_ht_dw(DwArgs a) {
         const float* Ga = a.G + ((size_t)l * 256 + u) * a.Np + c0 + 4 * h;
         const float* Hb = (l == 0 || from_x) ? nullptr
                                              : a.hsave + ((size_t)(l - 1) * 256 + kk) * a.Np + c0 + 4 * h;
+        // one load pair then its MFMAs per trip, not dw_rows' two-buffer
+        // prefetch: a wave has one or two 256-ray chunks, and through dw_rows
+        // this kernel measured 63.2 - 63.6 against 62.8 - 63.1 us (4,096 rays,
+        // four rounds of three alternating profiler passes per build)
         for (int m = 0; m < 32; ++m) {
             const float4 ga = *reinterpret_cast<const float4*>(Ga + 8 * m);
             if (kt == 0) bsum += (ga.x + ga.y) + (ga.z + ga.w);
-            float xb[4];
-            if (from_x) {
+            float4 xb;
+            if (from_x) {                                     // row-major rows, stride 164
+                float x[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const uint32_t ray = c0 + 8u * m + 4u * h + e;
-                    xb[e] = (xok && ray < a.N) ? a.rows[(size_t)ray * kRowIn + xc] : 0.0f;
+                    x[e] = (xok && ray < a.N) ? a.rows[(size_t)ray * kRowIn + xc] : 0.0f;
                 }
+                xb = make_float4(x[0], x[1], x[2], x[3]);
             } else {
-                const float4 hb = *reinterpret_cast<const float4*>(Hb + 8 * m);
-                xb[0] = hb.x; xb[1] = hb.y; xb[2] = hb.z; xb[3] = hb.w;
+                xb = *reinterpret_cast<const float4*>(Hb + 8 * m);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga.x, xb[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga.y, xb[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga.z, xb[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga.w, xb[3], acc, 0, 0, 0);
+            dw_mma(acc, ga, xb);
         }
     }
     if (kt == 0) {
         bsum = sum_halves(bsum);
         if (h == 0) sbias[((size_t)part * 5 + l) * 256 + u] = bsum;
     }
-    // acc register q of lane (col i, half h) = dW[32ut + (q & 3) + 8 (q >> 2) + 4h][32kt + i]
     float* const st = a.slab + ((size_t)part * kDwTiles + tile) * 1024;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) st[((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + i] = acc[q];
+    for (int q = 0; q < 16; ++q) st[dw_row(q, h) * 32 + i] = acc[q];
 }
 
 // the parts of every weight / bias / LN gradient added in part order into
@@ -444,7 +380,7 @@ __global__ void __launch_bounds__(256) k_ht_dw_sum(DwArgs a) {
         if (t >= base && t < base + n) {
             const uint32_t row = (t - base) / (uint32_t)kKl[l], col = (t - base) % (uint32_t)kKl[l];
             // padded input column of logical column col (layer 0: the same; layer 2: the same)
-            const uint32_t tile = (uint32_t)dw_items_before(l) + (row >> 5) * kDwTilesK[l] + (col >> 5);
+            const uint32_t tile = (uint32_t)kDw.before(l) + (row >> 5) * kDw.tiles_k[l] + (col >> 5);
             const size_t off = (size_t)tile * 1024 + (row & 31u) * 32 + (col & 31u);
             float sum = 0.0f;
             for (uint32_t p = 0; p < a.parts; ++p) sum += a.slab[(size_t)p * kDwSlabTile + off];
@@ -485,26 +421,18 @@ struct Layout {
     size_t bytes;
 };
 
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 Layout carve(uint32_t N, void* base) {
     Layout L{};
     L.Np = (N + 255u) & ~255u;
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* q = base ? reinterpret_cast<float*>(p + off) : nullptr;
-        off += al256(floats * sizeof(float));
-        return q;
-    };
-    L.wf = take(kPackFloats);
-    L.wb = take(kPackFloats);
-    L.hsave = take((size_t)5 * 256 * L.Np);
-    L.stats = take((size_t)2 * L.Np);
-    L.G = take((size_t)5 * 256 * L.Np);
-    L.lnpart = take((size_t)512 * div_up(N, kRays));
-    L.slab = take(dw_slab_floats(std::min<uint32_t>(L.Np / 256u, kDwParts)));
-    L.bytes = off;
+    Carver c(base);
+    L.wf = c.take(kPackFloats);
+    L.wb = c.take(kPackFloats);
+    L.hsave = c.take((size_t)5 * 256 * L.Np);
+    L.stats = c.take((size_t)2 * L.Np);
+    L.G = c.take((size_t)5 * 256 * L.Np);
+    L.lnpart = c.take((size_t)512 * div_up(N, kRays));
+    L.slab = c.take(dw_slab_floats(std::min<uint32_t>(L.Np / 256u, kDwParts)));
+    L.bytes = c.bytes();
     return L;
 }
 

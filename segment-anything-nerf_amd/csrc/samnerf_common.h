@@ -42,6 +42,22 @@ int check_background(uint32_t N, const char* what);
 
 inline uint32_t div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
+// A workspace carved into consecutive pieces, each starting on a 256-byte
+// boundary.  With a null base nothing is handed out and only the sizes add up:
+// the *_workspace_size entry points carve the same way as the calls.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+    template <typename T = float>
+    T* take(size_t floats) {              // the size in floats, whatever T
+        T* q = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (floats * sizeof(float) + 255) & ~(size_t)255;
+        return q;
+    }
+    size_t bytes() const { return off; }
+};
+
 // Hash primes of the coherent spatial hash (gridencoder.cu:49).
 constexpr uint32_t kPrime1 = 2654435761u;
 constexpr uint32_t kPrime2 = 805459861u;
