@@ -1078,6 +1078,59 @@ typedef struct {
  * H * W of 2^31 or more, an unknown input_type.  n == 0 is a successful no-op. */
 int samnerf_incoherent_masks(const samnerf_incoherent_masks_args* args, samnerf_stream_t stream);
 
+/* ---------------------------------------------------- distillation loss --
+ * The loss of Trainer.train_step's SAM-feature branch (nerf/utils.py:1094-1108):
+ * the rendered features pred [h*w][256] (ray-major, the render's samvit, 256
+ * wide as everywhere in this library) resized to the teacher's map gt
+ * [256][Hg][Wg], and their mean squared error.  Every size lies in [1, 1024].
+ *
+ * The resize is F.interpolate(mode='bilinear') with align_corners=False and no
+ * antialiasing.  The taps of destination cell d of an axis of n_in source and
+ * n_out destination cells are formed in fp32, in one place that the kernels
+ * and samnerf_bilinear_taps_host share:
+ *     scale = (float)n_in / n_out
+ *     src   = max(scale * (d + 0.5f) - 0.5f, 0)
+ *     i0 = (int)src,  i1 = i0 + (i0 < n_in - 1),  l1 = src - i0,  l0 = 1 - l1
+ * and a cell is  l0y * (l0x * v00 + l1x * v01) + l1y * (l0x * v10 + l1x * v11).
+ * These taps are this library's definition: ATen's own weights differ from
+ * them in the last bit at some size pairs, so results are compared with a
+ * float64 evaluation within a tolerance, never with torch for equality.
+ *
+ * loss = the mean over the 256 * Hg * Wg cells of (resized - gt)^2;
+ * grad_pred = grad_loss * d loss / d pred (resized carries no gradient).
+ * Nothing is copied to the host and nothing synchronises: the calls can be
+ * captured in a graph.  The forward leaves the per-axis taps, each source
+ * cell's run of destination cells and the scaled differences [Hg*Wg][256] in
+ * ws; the backward reads only ws and grad_loss, so it follows a forward with
+ * the same sizes and the same ws.
+ *
+ * Repeatable to the bit: no float atomics.  The loss is workgroup partials
+ * added in a fixed order; the backward is a gather in which every source cell
+ * adds its destination cells' differences row by row, column by column.  A
+ * source cell that no destination cell touches (6 of 16 columns at 16 -> 5)
+ * gets exactly 0.0f.  Non-finite inputs reach the loss as NaN or Inf; no
+ * cell-by-cell promise is made for them.
+ *
+ * SAMNERF_EINVAL: a size outside [1, 1024], a null pointer other than resized,
+ * pred / grad_pred / ws not 16-byte aligned; SAMNERF_EWORKSPACE: ws_bytes
+ * below the workspace size. */
+
+/* Bytes of workspace for these sizes (0 for invalid ones). */
+size_t samnerf_feat_loss_workspace_size(uint32_t h, uint32_t w, uint32_t Hg, uint32_t Wg);
+
+/* resized [256][Hg][Wg] or NULL; loss: 1 device float. */
+int samnerf_feat_loss_forward(const float* pred, uint32_t h, uint32_t w, const float* gt, uint32_t Hg,
+                              uint32_t Wg, float* resized, float* loss, void* ws, size_t ws_bytes,
+                              samnerf_stream_t stream);
+
+/* grad_loss: 1 device float; grad_pred [h*w][256] is overwritten. */
+int samnerf_feat_loss_backward(const float* grad_loss, uint32_t h, uint32_t w, uint32_t Hg, uint32_t Wg,
+                               float* grad_pred, void* ws, size_t ws_bytes, samnerf_stream_t stream);
+
+/* The taps of one axis on the host (no GPU): i0, i1, l1 [n_out].
+ * SAMNERF_EINVAL: a size outside [1, 1024] or a null pointer. */
+int samnerf_bilinear_taps_host(uint32_t n_in, uint32_t n_out, uint32_t* i0, uint32_t* i1, float* l1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,5 +5,6 @@
   dist      ray sharding over ranks + RCCL all-gather of output tiles
   batch     TrainBatchSampler: a training step's ray choice and collate gathers
   incoherent  the incoherent-region tables: from the GT masks, and the dynamic update
+  feat_loss   the distillation loss: bilinear resize to the teacher's map + MSE
 """
 from ._lib import EXPORTED, LIB_PATH, SamnerfUnavailable, lib  # noqa: F401

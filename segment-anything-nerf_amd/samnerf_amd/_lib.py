@@ -189,6 +189,11 @@ _SIGS = {
     "samnerf_eval_confusion": ([_vp, _vp, _u32, _u32, _vp, _vp], _int),
     "samnerf_incoherent_ids": ([ctypes.POINTER(SamnerfIncoherentIdsArgs), _vp], _int),
     "samnerf_incoherent_masks": ([ctypes.POINTER(SamnerfIncoherentMasksArgs), _vp], _int),
+    "samnerf_feat_loss_workspace_size": ([_u32, _u32, _u32, _u32], _sz),
+    "samnerf_feat_loss_forward": ([_vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp], _int),
+    "samnerf_feat_loss_backward": ([_vp, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp], _int),
+    "samnerf_bilinear_taps_host": ([_u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                    ctypes.POINTER(_f32)], _int),
 }
 
 

@@ -171,6 +171,21 @@ def sam_train_step(renderer, rays_o_lr, rays_d_lr, h, w, gt_samvit, cam_near_far
     return pred, F.mse_loss(pred, gt_samvit, reduction="none").mean()
 
 
+def sam_train_step_fused(renderer, rays_o_lr, rays_d_lr, h, w, gt_samvit, cam_near_far=None, view_width=0,
+                         resized=True):
+    """sam_train_step with the loss on the device as well: render_sam_train
+    plus samnerf_amd.feat_loss (csrc/feat_loss.hip) on the render's ray-major
+    rows -- no NCHW copy, no float atomics in the resize's gradient, so with
+    FusedRenderer(deterministic=True) the step repeats bit for bit at every
+    view size, not only where h x w is the teacher's.  Returns (pred
+    [1,256,h',w'] without gradient, or None with resized=False; loss)."""
+    from .feat_loss import feat_loss
+    from .fused import render_sam_train
+    out = render_sam_train(renderer, rays_o_lr, rays_d_lr, cam_near_far=cam_near_far, view_width=view_width)
+    loss, pred = feat_loss(out["samvit"], h, w, gt_samvit, resized=resized)
+    return pred, loss
+
+
 def mask_train_step(model, rays_o, rays_d, gt_mask, num_rays=None, cam_near_far=None):
     """Trainer.train_step's --with_mask branch (nerf/utils.py:941-977, 1026):
     render the instance logits (perturb off, proposal nets frozen, white
