@@ -1131,6 +1131,66 @@ int samnerf_feat_loss_backward(const float* grad_loss, uint32_t h, uint32_t w, u
  * SAMNERF_EINVAL: a size outside [1, 1024] or a null pointer. */
 int samnerf_bilinear_taps_host(uint32_t n_in, uint32_t n_out, uint32_t* i0, uint32_t* i1, float* l1);
 
+/* -------------------------------------------------------- teacher image --
+ * The SAM teacher's input from a render in device memory: what the reference
+ * does on the host between the full-resolution render and image_encoder
+ * (nerf/utils.py:1083-1085, :1203-1208; SamPredictor.set_image):
+ *     (pred_rgb.cpu().numpy() * 255).astype(uint8)
+ *     ResizeLongestSide(target).apply_image     PIL's 8-bit bilinear resize
+ *     Sam.preprocess                             (x - mean) / std, zero padding
+ * The bits are the contract: out_u8 equals PIL's Image.resize(BILINEAR) of the
+ * quantised render byte for byte, out_input equals the torch ops on it.
+ *
+ * Size (samnerf_teacher_image_shape, in double): scale = target / max(H, W),
+ * oh = (int)(H * scale + 0.5), ow = (int)(W * scale + 0.5).
+ *
+ * Quantise: u8 = (uint8)(int)(v * 255.0f), the fp32 product truncated, for v
+ * in [0, 1]; outside that range the result is the casts' and is not defined
+ * here.
+ *
+ * Resize: a horizontal pass and then a vertical pass, the intermediate image
+ * rounded to uint8 between them.  For an axis of `in` source and `out`
+ * destination cells, all in double:
+ *     scale = in / out,  fs = max(scale, 1),  support = fs,  ss = 1 / fs
+ *     center = (xx + 0.5) * scale
+ *     xmin = max(0, (int)(center - support + 0.5))
+ *     n    = min(in, (int)(center + support + 0.5)) - xmin
+ *     w[x] = 1 - a where a = |(x + xmin - center + 0.5) * ss| < 1, else 0
+ *     w[x] /= sum of w (when it is not 0);  k[x] = (int)(0.5 + w[x] * 4194304)
+ * and a pass writes clamp(((1 << 21) + sum k[x] * pixel[xmin + x]) >> 22, 0,
+ * 255), in int32, which cannot overflow.  The tables are built by a kernel
+ * from these expressions (truncating casts), not on the host.
+ *
+ * Input tensor: per channel c, ((float)u8 - mean[c]) / std[c] -- one fp32
+ * subtraction and one correctly rounded fp32 division -- written CHW into
+ * out_input [3][S][S]; every cell right of or below the image is +0.0f.
+ *
+ * samnerf_teacher_image only enqueues three launches on `stream`: no
+ * allocation, no copy to the host, no synchronisation; it can be captured in
+ * a graph.  No float atomics: the same inputs give the same bits.
+ *
+ * rgb: fp32 [H][W][3] on the device.  mean, std: three HOST floats each, NULL
+ * for SAM's registered buffers (123.675, 116.28, 103.53) and (58.395, 57.12,
+ * 57.375).  out_u8: uint8 [oh][ow][3] or NULL (what apply_image returns);
+ * out_input: fp32 [3][S][S] or NULL (what Sam.preprocess returns).  workspace:
+ * samnerf_teacher_image_workspace_size(H, W, oh, ow) bytes, 256-byte aligned.
+ *
+ * SAMNERF_EINVAL, before anything is launched or any pointer read: H, W, oh,
+ * ow (and S with out_input) outside [1, 8192]; a null rgb; out_u8 and
+ * out_input both NULL; S < max(oh, ow) with out_input; workspace NULL or
+ * workspace_bytes too small. */
+
+/* oh, ow for a longest side of `target`.  SAMNERF_EINVAL: H, W or target
+ * outside [1, 8192], a null pointer.  Host only. */
+int samnerf_teacher_image_shape(uint32_t H, uint32_t W, uint32_t target, uint32_t* oh, uint32_t* ow);
+
+/* Bytes of workspace for these sizes (0 for invalid ones).  Host only. */
+size_t samnerf_teacher_image_workspace_size(uint32_t H, uint32_t W, uint32_t oh, uint32_t ow);
+
+int samnerf_teacher_image(const float* rgb, uint32_t H, uint32_t W, uint32_t oh, uint32_t ow, uint32_t S,
+                          const float* mean, const float* std, uint8_t* out_u8, float* out_input,
+                          void* workspace, size_t workspace_bytes, samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,7 @@
 
 #include "block_reduce.h"
 #include "instance_row.h"
+#include "quantise.h"
 #include "samnerf_common.h"
 
 using namespace samnerf;
@@ -93,8 +94,6 @@ __device__ __forceinline__ float truth_of(const float* g, uint32_t C, uint32_t c
     const float a = g[3];
     return g[ch] * a + bg * (1.0f - a);
 }
-
-__device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)(int)(v * 255.0f); }
 
 __global__ void __launch_bounds__(kT) k_eval_rgb(Params P) {
     __shared__ double shd[kWaves];

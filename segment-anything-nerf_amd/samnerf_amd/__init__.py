@@ -6,5 +6,6 @@
   batch     TrainBatchSampler: a training step's ray choice and collate gathers
   incoherent  the incoherent-region tables: from the GT masks, and the dynamic update
   feat_loss   the distillation loss: bilinear resize to the teacher's map + MSE
+  teacher     the SAM teacher's input from a render on the device, set_image, the feature cache
 """
 from ._lib import EXPORTED, LIB_PATH, SamnerfUnavailable, lib  # noqa: F401

@@ -194,6 +194,10 @@ _SIGS = {
     "samnerf_feat_loss_backward": ([_vp, _u32, _u32, _u32, _u32, _vp, _vp, _sz, _vp], _int),
     "samnerf_bilinear_taps_host": ([_u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                     ctypes.POINTER(_f32)], _int),
+    "samnerf_teacher_image_shape": ([_u32, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)], _int),
+    "samnerf_teacher_image_workspace_size": ([_u32, _u32, _u32, _u32], _sz),
+    "samnerf_teacher_image": ([_vp, _u32, _u32, _u32, _u32, _u32, ctypes.POINTER(_f32), ctypes.POINTER(_f32),
+                               _vp, _vp, _vp, _sz, _vp], _int),
 }
 
 

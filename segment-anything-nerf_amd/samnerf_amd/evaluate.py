@@ -383,14 +383,16 @@ def _device_mean(stats, total, count):
     return torch.where(n > 0, s / n.clamp(min=1).to(torch.float64), torch.zeros_like(s)).to(torch.float32)
 
 
-def eval_step(model, data, opt, criterion=None, stats=None, sam_features=None):
+def eval_step(model, data, opt, criterion=None, stats=None, sam_features=None, predictor=None):
     """Trainer.eval_step (utils.py:1122-1241) on a model of this package:
     returns (pred_rgb, pred_depth, pred_extra, truth, loss) as the reference
     does -- the RGB branch (None, gt_rgb, MSE), --with_mask (pred_mask [H, W, K],
     gt_mask, the NLL; 0 under data['use_default_intrinsics']) and --with_sam
     without use_point (pred_samvit [1, 256, h, w], pred_rgb, the feature MSE;
     sam_features(image_uint8) -> gt_samvit [1, 256, h', w'] stands for the SAM
-    predictor).  criterion: None or an MSELoss (the reference's) goes to the
+    predictor; with predictor= instead, an object with SamPredictor's interface,
+    gt_samvit comes from teacher.set_image_from_render and the render never
+    leaves the device).  criterion: None or an MSELoss (the reference's) goes to the
     kernels; anything else is applied with torch ops.  stats: the record to
     fill (a row of an Evaluator's table).  On CUDA the loss is a device tensor
     derived from the record without a read-back."""
@@ -445,10 +447,15 @@ def eval_step(model, data, opt, criterion=None, stats=None, sam_features=None):
         return pred_rgb, pred_depth, pred_mask, gt_mask, loss
     if _o(opt, "use_point", False):
         raise NotImplementedError("eval_step: the use_point branch runs the SAM decoder (sam_bridge); not covered")
-    if sam_features is None:
-        raise ValueError("eval_step: --with_sam needs sam_features(image_uint8) -> gt_samvit [1, 256, h, w]")
-    image = (pred_rgb.detach().cpu().numpy() * 255).astype(np.uint8)
-    gt_samvit = sam_features(image)
+    if predictor is not None:
+        from .teacher import set_image_from_render
+        gt_samvit = set_image_from_render(predictor, pred_rgb.detach())
+    elif sam_features is None:
+        raise ValueError("eval_step: --with_sam needs sam_features(image_uint8) -> gt_samvit [1, 256, h, w], "
+                         "or predictor=")
+    else:
+        image = (pred_rgb.detach().cpu().numpy() * 255).astype(np.uint8)
+        gt_samvit = sam_features(image)
     h, w = int(data["h"]), int(data["w"])
     out2 = model.render(data["rays_o_lr"], data["rays_d_lr"], staged=False, index=data.get("index"), bg_color=1,
                         perturb=False, cam_near_far=cnf, return_feats=1, H=h, W=w)

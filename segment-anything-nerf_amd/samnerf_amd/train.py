@@ -186,6 +186,47 @@ def sam_train_step_fused(renderer, rays_o_lr, rays_d_lr, h, w, gt_samvit, cam_ne
     return pred, loss
 
 
+def sam_distill_step(model, renderer, data, opt, global_step, predictor, cache=None, perturb=True):
+    """Trainer.train_step's --with_sam branch whole (utils.py:872-889,
+    1072-1108), with the reference's `data` keys: rays_o, rays_d [H*W, 3], H, W
+    (the full-resolution view), rays_o_lr, rays_d_lr, h, w (the feature view)
+    and, optionally, index and cam_near_far.
+
+    cache: a teacher.FeatureCache (the Trainer's self.cache) or None.  Once it
+    is full, every step but each opt.cache_interval-th takes a cached batch
+    with its teacher features (teacher.use_cache_now).  On a miss the
+    full-resolution view is rendered under no_grad (staged, perturbed, the
+    proposal nets frozen), teacher.set_image_from_render hands it to the
+    predictor's image encoder on the device, and the batch goes into the cache
+    with its gt_samvit.  Then sam_train_step_fused on the feature rays.
+    Returns (pred_samvit, gt_samvit, loss); nothing in the step reads device
+    memory on the host."""
+    from .teacher import set_image_from_render, use_cache_now
+    use_cache = use_cache_now(opt, cache, global_step)
+    if use_cache:
+        data = cache.get()
+    cam_near_far = data["cam_near_far"] if "cam_near_far" in data else None
+    if use_cache:
+        gt_samvit = data["gt_samvit"]
+    else:
+        with torch.no_grad():
+            rays_o, rays_d = data["rays_o"], data["rays_d"]
+            H, W = int(data["H"]), int(data["W"])
+            N = rays_o.shape[0]
+            bg_color = torch.rand(N, 3, device=rays_o.device) if getattr(opt, "background", None) == "random" else 1
+            outputs = model.render(rays_o, rays_d, staged=True, index=data.get("index"), bg_color=bg_color,
+                                   perturb=perturb, cam_near_far=cam_near_far, update_proposal=False,
+                                   return_feats=0)
+            pred_rgb = outputs["image"].reshape(H, W, 3)
+            gt_samvit = set_image_from_render(predictor, pred_rgb)
+            if opt.cache_size > 0 and cache is not None:
+                data["gt_samvit"] = gt_samvit
+                cache.insert(data)
+    pred_samvit, loss = sam_train_step_fused(renderer, data["rays_o_lr"], data["rays_d_lr"], int(data["h"]),
+                                             int(data["w"]), gt_samvit, cam_near_far=cam_near_far)
+    return pred_samvit, gt_samvit, loss
+
+
 def mask_train_step(model, rays_o, rays_d, gt_mask, num_rays=None, cam_near_far=None):
     """Trainer.train_step's --with_mask branch (nerf/utils.py:941-977, 1026):
     render the instance logits (perturb off, proposal nets frozen, white
