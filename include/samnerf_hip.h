@@ -1191,6 +1191,106 @@ int samnerf_teacher_image(const float* rgb, uint32_t H, uint32_t W, uint32_t oh,
                           const float* mean, const float* std, uint8_t* out_u8, float* out_input,
                           void* workspace, size_t workspace_bytes, samnerf_stream_t stream);
 
+/* ---------------------------------------------------------- SAM decoder --
+ * SAM's prompt encoder and mask decoder for point prompts, and the
+ * postprocess of its masks: what SamPredictor.predict_torch runs between the
+ * image embedding and the masks when the prompt is points (no box, no mask
+ * input, one prompt set), with plain SAM's weights (no HQ token).  Written
+ * from the model's published description and tested against this project's
+ * own float64 restatement with synthetic weights; it has not been compared
+ * with an installed segment_anything or a real checkpoint.
+ *
+ * Sizes: C = 256 channels, 8 heads; g x g image tokens (g a multiple of 8 in
+ * [8, 64]; SAM's is 64), N = g*g; the input frame is S = 16 g; low-res masks
+ * are 4g x 4g.  P points in [1, 58], T = P + 6 tokens.
+ *
+ *   pe(c), c = (x, y) in [0,1]^2:  v = (2c - 1) @ G * 2 pi, cat(sin v, cos v)
+ *   image_pe[y*g + x] = pe(((x + .5) / g, (y + .5) / g))
+ *   point token = pe(((x + .5) / S, (y + .5) / S)) + point_embeddings[label];
+ *   one padding token = not_a_point_embed;
+ *   tokens = cat(iou_token, mask_tokens[4], points[P], pad), also query_pe
+ *   src = features + no_mask_embed
+ *   Attention(q, k, v; inner): 8 heads of inner / 8, softmax(q k^T /
+ *   sqrt(inner / 8)) v, out_proj; inner = 256 for the token self-attention
+ *   and 128 for every cross-attention
+ *   block l in {0, 1} (LayerNorm eps 1e-5, MLP lin2(relu(lin1 256 -> 2048))):
+ *     q = norm1(l == 0 ? self(q, q, q) : q + self(q + pe, q + pe, q))
+ *     q = norm2(q + t2i(q + query_pe, k + image_pe, k))
+ *     q = norm3(q + mlp(q))
+ *     k = norm4(k + i2t(k + image_pe, q + query_pe, q))
+ *   q = norm_final(q + final_t2i(q + query_pe, k + image_pe, k))
+ *   upscaled = gelu(convT2(gelu(LayerNorm2d(convT1(k as [256][g][g])))))
+ *     (2 x 2 stride-2 transposed convolutions 256 -> 64 -> 32, LayerNorm2d
+ *     over the channels of a pixel with eps 1e-6, the erf GELU)
+ *   hyper_i = MLP_i(q[1 + i]) (256 -> 256 -> 256 -> 32, ReLU between)
+ *   low_res[i] = hyper_i . upscaled;  iou = MLP(q[0]) (256 -> 256 -> 256 -> 4)
+ *
+ * Every product is an exact fp32 FMA accumulated in fp32; sin, cos, exp and
+ * erf are the accurate library functions.  No float atomics and every sum in a
+ * fixed order: the same inputs give the same bits.  Nothing is copied to the
+ * host and nothing synchronises; the points travel as kernel arguments.
+ *
+ * raw: the checkpoint's tensors as fp32, concatenated in this order, each in
+ * its state-dict shape (samnerf_sam_decoder_raw_count floats in all):
+ *   prompt_encoder: pe_layer.positional_encoding_gaussian_matrix [2][128],
+ *     point_embeddings.0, .1, not_a_point_embed, no_mask_embed [256] each;
+ *   mask_decoder: iou_token [256], mask_tokens [4][256];
+ *   transformer.layers.0, then .1: self_attn, cross_attn_token_to_image,
+ *     cross_attn_image_to_token (each q_proj, k_proj, v_proj, out_proj as
+ *     weight then bias), norm1 .. norm4 (weight, bias), mlp.lin1, mlp.lin2
+ *     (weight, bias);
+ *   transformer.final_attn_token_to_image (as above), norm_final_attn;
+ *   output_upscaling.0 (weight [256][64][2][2], bias), .1 (weight, bias),
+ *     .3 (weight [64][32][2][2], bias);
+ *   output_hypernetworks_mlps.0 .. 3, each layers.0 .. 2 (weight, bias);
+ *   iou_prediction_head.layers.0 .. 2 (weight, bias).
+ * samnerf_sam_decoder_pack turns them into the kernels' order (linear weights
+ * as [in][out], the transposed convolutions pixel-major) and adds the image_pe
+ * table of g; once per checkpoint and g.
+ *
+ * SAMNERF_EINVAL, before anything is launched: g not a multiple of 8 in
+ * [8, 64]; P outside [1, 58]; a label other than 0 or 1; a null pointer (the
+ * workspace included); pack, iou or workspace not 16-byte aligned; a pack
+ * smaller than samnerf_sam_decoder_pack_size(g); h, w not both 0 or both in
+ * [1, 1024].  SAMNERF_EWORKSPACE: workspace_bytes (or pack_bytes, when
+ * packing) too small. */
+
+/* Floats of `raw`.  Host only. */
+size_t samnerf_sam_decoder_raw_count(void);
+
+/* Bytes of the pack for g (0 for an invalid g).  Host only. */
+size_t samnerf_sam_decoder_pack_size(uint32_t g);
+
+int samnerf_sam_decoder_pack(const float* raw, size_t raw_count, uint32_t g, void* pack, size_t pack_bytes,
+                             samnerf_stream_t stream);
+
+/* Bytes of workspace for g (0 for an invalid g).  Host only. */
+size_t samnerf_sam_decoder_workspace_size(uint32_t g);
+
+/* features: h = w = 0: the image tokens [g*g][256], token-major (zero where
+ * the view is padded); otherwise a rendered map [h][w][256], which the first
+ * kernel resizes to a long side of g (vh = (int)(h * r), vw = (int)(w * r),
+ * r = g / max(h, w) in double; the taps of the distillation loss above) and
+ * pads with zeros.  points: P HOST (x, y) pairs in the S frame; labels: P HOST
+ * values 0 or 1.  low_res [4][4g][4g] and iou [4] on the device: mask 0 is
+ * multimask_output=False's, masks 1 .. 3 multimask_output=True's. */
+int samnerf_sam_decoder(const void* pack, size_t pack_bytes, uint32_t g, const float* features, uint32_t h,
+                        uint32_t w, const int32_t* points, const int32_t* labels, uint32_t P, float* low_res,
+                        float* iou, void* workspace, size_t workspace_bytes, samnerf_stream_t stream);
+
+/* Kernel launches of the last successful samnerf_sam_decoder call. */
+int samnerf_sam_decoder_launches(void);
+
+/* Sam.postprocess_masks in one launch: low_res [M][4g][4g] (M in [1, 4])
+ * resized to S x S (bilinear, align_corners=False), cropped to (in_h, in_w),
+ * resized to (H, W): 16 taps per output pixel with the taps above, the S x S
+ * image never written.  logits fp32 [M][H][W] and / or mask uint8 [M][H][W]
+ * (logit > 0); one of them may be NULL.  SAMNERF_EINVAL: g as above, M outside
+ * [1, 4], in_h or in_w outside [1, S], H or W outside [1, 8192], a null
+ * low_res, both outputs NULL. */
+int samnerf_sam_masks(const float* low_res, uint32_t M, uint32_t g, uint32_t in_h, uint32_t in_w, uint32_t H,
+                      uint32_t W, float* logits, uint8_t* mask, samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

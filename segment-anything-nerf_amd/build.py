@@ -30,7 +30,7 @@ SOURCES = ["common.cpp", "grid_encoder.hip", "sh_freq_encoder.hip", "raymarch.hi
            "sam_head.hip", "tile_codec.hip", "train_optim.hip", "sam_head_train.hip",
            "mask_head.hip", "rgb_train.hip", "mask_head_train.hip", "perturb.hip",
            "mask_loss.hip", "batch_sampler.hip", "present.hip", "evaluate.hip",
-           "incoherent.hip", "feat_loss.hip", "teacher_image.hip"]
+           "incoherent.hip", "feat_loss.hip", "teacher_image.hip", "sam_decoder.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-unused-variable",

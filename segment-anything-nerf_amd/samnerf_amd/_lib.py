@@ -198,6 +198,14 @@ _SIGS = {
     "samnerf_teacher_image_workspace_size": ([_u32, _u32, _u32, _u32], _sz),
     "samnerf_teacher_image": ([_vp, _u32, _u32, _u32, _u32, _u32, ctypes.POINTER(_f32), ctypes.POINTER(_f32),
                                _vp, _vp, _vp, _sz, _vp], _int),
+    "samnerf_sam_decoder_raw_count": ([], _sz),
+    "samnerf_sam_decoder_pack_size": ([_u32], _sz),
+    "samnerf_sam_decoder_pack": ([_vp, _sz, _u32, _vp, _sz, _vp], _int),
+    "samnerf_sam_decoder_workspace_size": ([_u32], _sz),
+    "samnerf_sam_decoder": ([_vp, _sz, _u32, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_int32),
+                             ctypes.POINTER(ctypes.c_int32), _u32, _vp, _vp, _vp, _sz, _vp], _int),
+    "samnerf_sam_decoder_launches": ([], _int),
+    "samnerf_sam_masks": ([_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp], _int),
 }
 
 

@@ -11,6 +11,11 @@ object with SamPredictor's interface (reset_image, original_size, input_size,
 features, is_image_set, interm_features, predict_torch), so a ROCm build of
 SAM plugs in unchanged.  Nothing leaves the device: the features stay the
 render's tensor, resized and padded on the GPU.
+
+`sam_predict_device` is the same hand-off to the project's own decoder
+(sam_decoder.SamDecoder: SAM's prompt encoder and mask decoder for point
+prompts as HIP kernels), which also serves `sam_predict` through
+sam_decoder.DevicePredictor.
 """
 import numpy as np
 import torch
@@ -74,6 +79,26 @@ def sam_predict(predictor, H, W, features, point_coords=None, mask_input=None, d
                                                    multimask_output=False)
     original = (pts / r).astype(np.int32)
     return masks[0], original, low_res[0]
+
+
+def sam_predict_device(decoder, H, W, samvit_hwc, point_coords=None, rng=None):
+    """sam_predict on a sam_decoder.SamDecoder with the rendered map as it is:
+    samvit_hwc [h, w, 256] (the render's samvit viewed as rows of the h x w
+    view) goes to the decoder's first kernel, which resizes its long side to
+    the token grid and pads it -- no F.interpolate, no permute, and no host
+    copy but the click coordinates.  Same return as sam_predict."""
+    S = decoder.S
+    r = S / W if W > H else S / H
+    input_size = (int(H * r), int(W * r))
+    if point_coords is None:
+        if S != 1024:
+            raise ValueError("sam_predict_device: a random click is drawn in the 1024 frame (g = 64)")
+        pts, _ = click_coords(H, W, None, rng)
+    else:
+        pts = (np.asarray(point_coords).astype(np.float32) * r).astype(np.int32)
+    low_res, _iou = decoder.decode(samvit_hwc.contiguous(), pts)
+    masks = decoder.masks(low_res[:1], input_size, (H, W))
+    return masks, (pts / r).astype(np.int32), low_res[:1]
 
 
 class PromptMemory:
