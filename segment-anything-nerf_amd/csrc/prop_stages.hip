@@ -1,7 +1,7 @@
 // prop_stages.hip -- the two proposal stages of the fused render (the map of
-// the pipeline is in raymarch.hip): k_snf, k_prop_sigma, k_prop_pdf, the
-// one-kernel diagnostic form k_prop_fused, and their one host path
-// (run_proposal_stages), which the render and the RGB training step share.
+// the pipeline is in raymarch.hip): k_snf, k_prop_sigma, k_prop_pdf and their
+// one host path (run_proposal_stages), which the render and the RGB training
+// step share.
 #include <cmath>
 #include <cstdlib>
 
@@ -9,7 +9,6 @@
 #include "raymarch_device.h"
 #include "render_args.h"
 #include "samnerf_common.h"
-#include "wave_box.h"
 
 using namespace samnerf;
 
@@ -139,15 +138,10 @@ constexpr uint32_t prop_sigma_blocks(uint32_t N) {
 
 //
 // LOOK = kLookPacked / kLookRef: direct corner gathers (lookup_level3 /
-// lookup_level3_ref).  LOOK = kLookBox4: de-duplicated gathers (wave_box.h):
-// the 64 positions of a wave span a few cells of each proposal level (the
-// padded corner box of a 512^2 view's wave holds at most 64 rows at every
-// level), so the wave loads each level's box once (one row per lane) into
-// its LDS slice and reads its 40 corners from there: 5 vector-memory
-// instructions per sample instead of 40.  Same rows, weights and FMA order:
-// identical bits.
-constexpr uint32_t kPropBoxSlots = 128;      // rows per level slice (8 B each)
-
+// lookup_level3_ref).  A form with wave_box.h's de-duplicated gathers (each
+// level's box staged once per wave in LDS) gave the same bits and measured
+// 0.88 vs 0.83 ms (retired forms).
+//
 // KD / KH (round 5): the proposal grid's level classes as compile-time
 // masks (bit l: level l dense / hashed; the reference's proposal grids,
 // network.py:96-104 at the default sizes, are DDDHH and DDHHH), with a
@@ -181,11 +175,8 @@ k_prop_sigma(PropArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t r0 = g * 64u + lane, k = q * 4u + (threadIdx.x >> 6);
     if (g * 64u >= a.N) return;                     // whole wave past the end
-    // box form: every lane stays active for the wave reductions (lanes past
-    // the end recompute ray N - 1 and store nothing)
-    if (LOOK != kLookBox4 && r0 >= a.N) return;
-    const bool live = r0 < a.N;
-    const uint32_t r = live ? r0 : a.N - 1u;              // slot
+    if (r0 >= a.N) return;
+    const uint32_t r = r0;                                // slot
     const uint32_t N = a.N;
     // the LAY forms read k_snf's slot-ordered ray record (the ray id is then
     // needed only for perturb's per-ray bins); the others map slot -> ray
@@ -228,44 +219,7 @@ k_prop_sigma(PropArgs a) {
     float x = o[0] + d[0] * t, y = o[1] + d[1] * t, z = o[2] + d[2] * t;
     contract3(x, y, z);
     float feat[10];
-    if constexpr (LOOK == kLookBox4) {
-        __shared__ float2 smem[4][5 * kPropBoxSlots];
-        float* slice = reinterpret_cast<float*>(smem[threadIdx.x >> 6]);
-        const float ux = a.gs(x), uy = a.gs(y), uz = a.gs(z);
-        const URange ur = wave_urange(ux, uy, uz);
-        const bool ordered = wave_positions_ordered(ux, uy, uz);
-        // lane l < 5 sizes level l's box (pbox_lane reads res, fres, ftop)
-        const LevelDesc* lv = a.grid.lv;
-        LevelDesc mine = lv[0];
-#pragma unroll
-        for (int l = 1; l < 5; ++l) {
-            const bool me = lane == (uint32_t)l;
-            mine.res = me ? lv[l].res : mine.res;
-            mine.fres = me ? lv[l].fres : mine.fres;
-            mine.ftop = me ? lv[l].ftop : mine.ftop;
-        }
-        uint32_t p0, p1, p2;
-        pbox_lane(mine, ur, p0, p1, p2);
-        PBox bx[5];
-#pragma unroll
-        for (int l = 0; l < 5; ++l) bx[l] = pbox_read(p0, p1, p2, l);
-        const char* base = reinterpret_cast<const char*>(a.grid.emb);
-#pragma unroll
-        for (int l = 0; l < 5; ++l)
-            if (bx[l].slots <= kPropBoxSlots)
-                stage_pbox<2>(base, a.grid.lv[l], bx[l], slice + l * kPropBoxSlots * 2, lane);
-        wave_lds_sync();
-#pragma unroll
-        for (int l = 0; l < 5; ++l) {
-            const float* sl = slice + l * kPropBoxSlots * 2;
-            if (bx[l].slots > kPropBoxSlots)
-                lookup_level3<2>(a.grid.emb, a.grid.lv[l], ux, uy, uz, feat + 2 * l);
-            else if (ordered)
-                lookup_level3_pbox<2, false>(a.grid.emb, a.grid.lv[l], bx[l], sl, ux, uy, uz, feat + 2 * l);
-            else
-                lookup_level3_pbox<2, true>(a.grid.emb, a.grid.lv[l], bx[l], sl, ux, uy, uz, feat + 2 * l);
-        }
-    } else if constexpr ((KD | KH) == 0x1Fu && LOOK == kLookPacked) {
+    if constexpr ((KD | KH) == 0x1Fu && LOOK == kLookPacked) {
         prop_lookup_lay<KD, KH>(a, x, y, z, feat);
     } else {
         grid_features<5, 2, LOOK == kLookRef>(a.grid, a.gs(x), a.gs(y), a.gs(z), feat);
@@ -276,7 +230,7 @@ k_prop_sigma(PropArgs a) {
     dense<1, 16, false>(a.W1, h, &sv);
     // the only store, after the weight reads: an earlier store could alias
     // W0/W1 and would demote the uniform weight reads to per-lane vector loads
-    if (live) a.wtmp[(size_t)k * N + r] = (rb_next - rb_prev) * expf(sv);          // trunc_exp forward
+    a.wtmp[(size_t)k * N + r] = (rb_next - rb_prev) * expf(sv);          // trunc_exp forward
 }
 
 // Stage 0 ray setup, one thread per ray: near/far from the AABB slab test
@@ -597,56 +551,6 @@ __device__ __forceinline__ void prop_pdf_phases(const PropArgs& a, float* sw, ui
     }
 }
 
-// The proposal stage in one kernel (round 2, DESIGN.md 5 "intermediates"): a
-// block owns 64 ray slots and all T samples -- wave w evaluates samples w,
-// w + 4, .. of its 64 rays (each ray's origin, direction and near/far loaded
-// once, not once per sample) and writes ds into the LDS rows k_prop_pdf
-// staged from HBM -- then the same pdf phases.  ds ([T][N], 134 MB per 512^2
-// view at T = 128) never leaves the CU.  Bit-identical to the two-kernel form
-// but 1.9x slower (prop0 1.10 vs 0.59 ms): 33 KB of LDS and 125 VGPRs per
-// block leave 4 waves per SIMD instead of k_prop_sigma's 8 to hide the gather
-// latency, and the serial pdf phase holds the block's slots while 3 of its 4
-// waves wait at the barrier.  A selectable variant (SAMNERF_PROP_FUSED=1).
-// PHX: its seeded form (a diagnostic variant like the kernel itself: two
-// generator calls per sample, not amortised).
-template <int T, int TN, bool FIRST, bool PHX = false>
-__global__ void __launch_bounds__(256) k_prop_fused(PropArgs a) {
-    constexpr int SW = T + 1;
-    __shared__ float sw[64 * SW];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, part = tid >> 6;
-    const uint32_t r0 = xcd_chunk(blockIdx.x, (a.N + 63u) / 64u) * 64u, N = a.N;
-    if (r0 >= N) return;
-    const uint32_t nr = min(64u, N - r0);
-    if (lane < nr) {
-        const uint32_t r = r0 + lane, ray = a.tiles(r);
-        float o[3], d[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            o[c] = a.rays_o[(size_t)ray * 3 + c];
-            d[c] = a.rays_d[(size_t)ray * 3 + c];
-        }
-        const float sn = a.snf[r], sf = a.snf[N + r];
-        float* row = sw + lane * SW;
-#pragma unroll 2
-        for (int kk = 0; kk < T / 4; ++kk) {
-            const int k = (int)part + 4 * kk;
-            const float b0 = stage_bin<T, FIRST, PHX>(a, k, r, ray), b1 = stage_bin<T, FIRST, PHX>(a, k + 1, r, ray);
-            const float rb_prev = real_bin(sn, sf, b0), rb_next = real_bin(sn, sf, b1);
-            const float t = (rb_next + rb_prev) / 2.0f;
-            float x = o[0] + d[0] * t, y = o[1] + d[1] * t, z = o[2] + d[2] * t;
-            contract3(x, y, z);
-            float feat[10];
-            grid_features<5, 2, false>(a.grid, a.gs(x), a.gs(y), a.gs(z), feat);
-            float h[16], sv;
-            dense_pk<16, 10, true>(a.W0, feat, h);
-            dense<1, 16, false>(a.W1, h, &sv);
-            row[k] = (rb_next - rb_prev) * expf(sv);      // trunc_exp forward
-        }
-    }
-    __syncthreads();
-    prop_pdf_phases<T, TN, FIRST, PHX>(a, sw, r0, nr);
-}
-
 // k_prop_sigma's lookup with compile-time level classes (KD / KH): the 5
 // levels' loads issued together, then the packed corner sums.
 // Uniform cells (round 5): a dense level whose cell is the same for all the
@@ -840,23 +744,18 @@ uint32_t launch_prop_sigma(int look, uint32_t N, hipStream_t s, const PropArgs& 
         return kd | kh << 8;
     }
     if (look == kLookRef) k_prop_sigma<T, FIRST, kLookRef, 0u, 0u, PHX><<<nb, 256, 0, s>>>(pa);
-    else if (look == kLookBox4 && box4_ok(pa.grid))
-        k_prop_sigma<T, FIRST, kLookBox4, 0u, 0u, PHX><<<nb, 256, 0, s>>>(pa);
     else k_prop_sigma<T, FIRST, kLookPacked, 0u, 0u, PHX><<<nb, 256, 0, s>>>(pa);
     return 0u;
 }
 
-// One proposal stage: ds per sample, then the pdf -- or both in k_prop_fused.
+// One proposal stage: ds per sample, then the pdf.  (One kernel for both, ds
+// kept in LDS, gave the same bits 1.9x slower: prop0 1.10 vs 0.59 ms per view,
+// DESIGN.md 5.)
 // PHX: the seeded kernel forms (only stage 0's sigma kernel reads positions).
 template <int T, int TN, bool FIRST, bool PHX>
-void run_stage(const PropArgs& pa, int look, bool fused, hipStream_t s, uint32_t& form) {
-    const uint32_t nb = xcd_blocks(div_up(pa.N, 64));
-    if (fused) {
-        k_prop_fused<T, TN, FIRST, PHX><<<nb, 256, 0, s>>>(pa);
-    } else {
-        form = launch_prop_sigma<T, FIRST, FIRST && PHX>(look, pa.N, s, pa);
-        k_prop_pdf<T, TN, FIRST, PHX><<<nb, 256, 0, s>>>(pa);
-    }
+void run_stage(const PropArgs& pa, int look, hipStream_t s, uint32_t& form) {
+    form = launch_prop_sigma<T, FIRST, FIRST && PHX>(look, pa.N, s, pa);
+    k_prop_pdf<T, TN, FIRST, PHX><<<xcd_blocks(div_up(pa.N, 64)), 256, 0, s>>>(pa);
 }
 
 void set_stage(PropArgs& pa, const samnerf_model* m, int i, const ProposalRun::Stage& st) {
@@ -891,11 +790,6 @@ void run_proposal_stages(const samnerf_model* m, uint32_t N, const ProposalRun& 
     pa.snf = r.snf;
     pa.rec = r.rec;
     pa.last_inf = current_background().background == 0 ? 1u : 0u;
-    // SAMNERF_PROP_FUSED=1: one kernel per proposal stage, ds kept in LDS
-    // (k_prop_fused; bit-identical, but measured 1.9x slower -- prop0 1.10 vs
-    // 0.59 ms per view -- so the two-kernel form stays the default)
-    const char* pfv = diag_env("SAMNERF_PROP_FUSED");
-    const bool fused = r.may_fuse && r.look == kLookAuto && pfv && pfv[0] == '1';
 
     // stage 0: 128 uniform samples -> 65 bins (renderer.py:263-267, :274-275)
     set_stage(pa, m, 0, r.st[0]);
@@ -907,16 +801,16 @@ void run_proposal_stages(const samnerf_model* m, uint32_t N, const ProposalRun& 
     const bool phx = m->perturb_device != 0;
     pa.phx = make_perturb_key(m->perturb_seed, m->perturb_offset);
     k_snf<<<div_up(N, 256), 256, 0, s>>>(pa);
-    if (phx) run_stage<128, 65, true, true>(pa, r.look, fused, s, forms[0]);
-    else run_stage<128, 65, true, false>(pa, r.look, fused, s, forms[0]);
+    if (phx) run_stage<128, 65, true, true>(pa, r.look, s, forms[0]);
+    else run_stage<128, 65, true, false>(pa, r.look, s, forms[0]);
 
     // stage 1: 64 samples -> 33 bins
     set_stage(pa, m, 1, r.st[1]);
     pa.u = make_lin((float)(0.5 / 33), (float)(1.0 - 0.5 / 33), 33);
     pa.bins_in = r.st[0].bins_out;
     if (r.mark) r.mark(1, s);
-    if (phx) run_stage<64, 33, false, true>(pa, r.look, fused, s, forms[1]);
-    else run_stage<64, 33, false, false>(pa, r.look, fused, s, forms[1]);
+    if (phx) run_stage<64, 33, false, true>(pa, r.look, s, forms[1]);
+    else run_stage<64, 33, false, false>(pa, r.look, s, forms[1]);
 }
 
 // The proposal stages of a training render (rgb_train.hip): the same kernels

@@ -231,13 +231,6 @@ Workspace carve(const samnerf_model* m, uint32_t N, void* base) {
     w.aeff = c.take(madapt ? (size_t)32 * kAeff : 0);
     w.mlog = c.take(madapt ? (size_t)m->mask_out * n : 0);
     w.xsum = c.take(madapt && m->with_mask == 2 ? (size_t)kAeff * n : 0);   // training renders only
-    const bool n1 = m->t_thresh > 0.0f;
-    w.n1_list = c.take<uint32_t>(n1 ? 2 * n : 0);
-    w.n1_cnt = c.take<uint32_t>(n1 ? 2 : 0);
-    w.n1_mask = c.take<uint64_t>(n1 ? 2 * ((n + 31) / 32) : 0);
-    w.n1_base = c.take<uint32_t>(n1 ? (n + 31) / 32 : 0);
-    w.n1_std = c.take<double>(n1 ? 6 * n : 0);
-    w.n1_stf = c.take(n1 ? 16 * n : 0);
     w.bytes = c.bytes();
     return w;
 }
@@ -418,7 +411,6 @@ int render_impl(const samnerf_model* m, const float* rays_o, const float* rays_d
     pr.n_cnf = n_cnf;
     pr.tiles = tiles;
     pr.look = look;
-    pr.may_fuse = !g_taps_on;
     pr.mark = mark_stage;
     pr.snf = w.snf;
     pr.rec = w.rec;

@@ -104,12 +104,6 @@ struct Workspace {
     float* aeff;       // [K][240] adaptive heads' effective matrix (with_mask, kinds 1-2)
     float* mlog;       // [N][K] adaptive heads' logits (with_mask, kinds 1-2)
     float* xsum;       // [N][kAeff] their per-ray input sums (with_mask, kinds 1-2; training)
-    uint32_t* n1_list; // [2][N] N1 compaction: the passes' slot lists (t_thresh > 0)
-    uint32_t* n1_cnt;  // [2] their lengths
-    uint64_t* n1_mask; // [ceil(N / 32)] the waves' ballot masks of open rays
-    uint32_t* n1_base; // [ceil(N / 32)] their exclusive scan
-    double* n1_std;    // [3][N] running optical depth / sum w / sum w t of open rays
-    float* n1_stf;     // [16][N] running sum w * grid_mlp rows
     size_t bytes;
 };
 
@@ -132,7 +126,6 @@ struct ProposalRun {
     uint32_t n_cnf;
     RayTiles tiles;          // slot -> ray
     int look;                // gather form (lookup_mode, or kLookPacked)
-    bool may_fuse;           // SAMNERF_PROP_FUSED may pick k_prop_fused (diagnostic build)
     StageMark mark;          // stage marks 0 and 1, or null
     float* snf;              // [2][N]
     float4* rec;             // [N][2] slot-ordered ray records, or null

@@ -2,9 +2,7 @@
 // is in raymarch.hip): the forward forms k_sgrid / k_sgrid_box4 with their
 // choice (launch_sgrid), and the distillation step's backward with its
 // deterministic variant.
-#include <algorithm>
 #include <cstdlib>
-#include <cstring>
 
 #include "f16x3.h"
 #include "render_args.h"
@@ -290,21 +288,12 @@ k_sgrid_box4(SgridArgs a) {
 //
 // The global float atomics are the cost: they execute at the memory side at
 // roughly one wave-instruction per 50 ns per CU whatever the lanes hold
-// (MI355X_MICROARCH.md), and the round-1 form issued 8 per wave and sample (one
-// per corner, duplicates among the 8 rays merged by a butterfly).  Here the
-// wave first sums its 64 corner contributions per channel in LDS over the
-// exact box of corner cells the 8 rays touch (wave_box.h's idea, reversed),
-// then compacts the non-zero cells (ballot + prefix) and adds each distinct
-// cell row once: ceil(distinct rows / 8) atomics per wave and sample --
-// ~2.4x fewer over the 16 levels of a training view (distinct corner rows of
-// 8 rays: ~10 at the coarse levels, ~50 at level 15).  Boxes of more than 64
-// cells (scattered rays) take the per-corner form.  Measured on a cfg-5 step
-// the box form is SLOWER (0.70 vs 0.56 ms): the atomic instruction count is
-// not what binds the per-corner form; the box's six wave reductions, LDS
-// atomics and three wave syncs per sample cost more than the atomics they
-// save.  The per-corner form stays the default (max_cells = 0); the box form
-// is kept selectable (SAMNERF_SGRID_BWD=box) and tested against it.
-constexpr uint32_t kBwdBoxCells = 64;
+// (MI355X_MICROARCH.md); 8 are issued per wave and sample, one per corner,
+// duplicates among the 8 rays merged by a butterfly.  Summing the wave's
+// corners over their box of cells in LDS first measured slower on a cfg-5
+// step (0.70 vs 0.56 ms), merging along the ray too (1.62 / 1.50 vs 1.29 ms),
+// and splitting a ray's samples over 4-16 blocks no faster (DESIGN.md,
+// retired forms).
 
 // DET (samnerf_sgrid_backward_det): the per-corner form's adds go
 // to a 64-bit fixed-point accumulator instead of the fp32 table -- integer
@@ -340,12 +329,9 @@ template <int T, bool DET = false>
 __global__ void __launch_bounds__(256)
 k_sgrid_backward(uint32_t N, RayTiles tiles, GridDesc<16> g, const float* __restrict__ u_in,
                  const float* __restrict__ w_in, const float* __restrict__ grad, uint32_t gstride,
-                 float* __restrict__ gemb, uint32_t max_cells, uint32_t run_res, DetAcc det = {}) {
-    __shared__ float box[4][kBwdBoxCells * 8];           // per wave: cell x channel sums
-    __shared__ uint32_t list[4][kBwdBoxCells];           // per wave: rows of the non-zero cells
+                 float* __restrict__ gemb, DetAcc det = {}) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t r = (uint32_t)(t >> 3), ch = (uint32_t)(t & 7u), lane = threadIdx.x & 63u;
-    const uint32_t wv = threadIdx.x >> 6;
     const uint32_t level = blockIdx.y;
     if (((t & ~(uint64_t)63) >> 3) >= N) return;          // whole wave past the end
     const bool live = r < N;                                // lanes stay for the reductions
@@ -353,29 +339,11 @@ k_sgrid_backward(uint32_t N, RayTiles tiles, GridDesc<16> g, const float* __rest
     const LevelDesc d = g.lv[level];
     const float gv = live ? grad[(size_t)tiles(rr) * gstride + level * 8u + ch] : 0.0f;
     float* base = gemb + (size_t)d.off * 8u + ch;
-    float* slice = box[wv];
-    uint32_t* rows = list[wv];
     const uint32_t top = d.res - 1u;
-    // blockIdx.z: this block's share of the samples (more waves in flight: the
-    // per-sample chain -- loads, box reductions, LDS sums, atomics -- is
-    // latency-bound at 8 rays per wave)
-    const int k0 = (int)(blockIdx.z * T / gridDim.z), k1 = (int)((blockIdx.z + 1) * T / gridDim.z);
-    // levels up to run_res: a lane walks its ray's samples in order, and the
-    // previous sample's 8 corner rows stay pending in registers -- a new corner
-    // on a pending row absorbs its sum, only rows the ray has left are added to
-    // memory (consecutive samples of a ray share cells at the coarse levels)
-    const bool run = !DET && max_cells == 0u && d.res <= run_res;     // block-uniform
     const bool fixed = DET && !sgrid_det_nonfinite(det);  // uniform: the header word
     const double dscale = fixed ? ldexp(1.0, sgrid_det_shift(det)) : 0.0;
     unsigned long long* const dbase = fixed ? det.acc + (size_t)d.off * 8u + ch : nullptr;
-    uint32_t prow[8];
-    float pval[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        prow[c] = 0xFFFFFFFFu;
-        pval[c] = 0.0f;
-    }
-    for (int k = k0; k < k1; ++k) {
+    for (int k = 0; k < T; ++k) {
         const float ux = u_in[((size_t)k * 3 + 0) * N + rr];
         const float uy = u_in[((size_t)k * 3 + 1) * N + rr];
         const float uz = u_in[((size_t)k * 3 + 2) * N + rr];
@@ -388,117 +356,36 @@ k_sgrid_backward(uint32_t N, RayTiles tiles, GridDesc<16> g, const float* __rest
         locate_axis(uy, d, cy, fy);
         locate_axis(uz, d, cz, fz);
         const uint32_t nx = min(cx + 1u, top), ny = min(cy + 1u, top), nz = min(cz + 1u, top);
-        // the wave's box of corner cells (cells are never negative: int order)
-        const uint32_t x0 = (uint32_t)wave_imin((int)cx), x1 = (uint32_t)wave_imax((int)nx);
-        const uint32_t y0 = (uint32_t)wave_imin((int)cy), y1 = (uint32_t)wave_imax((int)ny);
-        const uint32_t z0 = (uint32_t)wave_imin((int)cz), z1 = (uint32_t)wave_imax((int)nz);
-        const uint32_t ex = x1 - x0 + 1u, ey = y1 - y0 + 1u, ez = z1 - z0 + 1u;
-        const uint32_t cells = ex * ey * ez;                 // wave-uniform
-        if (!DET && cells <= max_cells) {
-            // 1. zero the slice (lane = cell), 2. LDS-add the corners
-            reinterpret_cast<float4*>(slice + lane * 8u)[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            reinterpret_cast<float4*>(slice + lane * 8u)[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            wave_lds_sync();
-            const uint32_t X[2] = {cx - x0, nx - x0};
-            const uint32_t Y[2] = {(cy - y0) * ex, (ny - y0) * ex};
-            const uint32_t Z[2] = {(cz - z0) * ex * ey, (nz - z0) * ex * ey};
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float wx = (c & 1) ? fx : 1.0f - fx;
-                const float wy = (c & 2) ? fy : 1.0f - fy;
-                const float wz = (c & 4) ? fz : 1.0f - fz;
-                const uint32_t cell = X[c & 1] + Y[(c >> 1) & 1] + Z[c >> 2];
-                atomicAdd(slice + cell * 8u + ch, ((wx * wy) * wz) * wg);
-            }
-            wave_lds_sync();
-            // 3. compact the non-zero cells (lane = cell): ballot + prefix
-            const float4 va = reinterpret_cast<const float4*>(slice + lane * 8u)[0];
-            const float4 vb = reinterpret_cast<const float4*>(slice + lane * 8u)[1];
-            const bool nzc = lane < cells && (va.x != 0.0f || va.y != 0.0f || va.z != 0.0f ||
-                                              va.w != 0.0f || vb.x != 0.0f || vb.y != 0.0f ||
-                                              vb.z != 0.0f || vb.w != 0.0f);
-            const uint64_t mask = __builtin_amdgcn_ballot_w64(nzc);
-            const uint32_t n = (uint32_t)__builtin_popcountll(mask);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-            if (nzc) {
-                const uint32_t bx = lane % ex, by = (lane / ex) % ey, bz = lane / (ex * ey);
-                rows[rank] = (dense_or_hash_row(x0 + bx, y0 + by, z0 + bz, d) << 6) | lane;
-            }
-            wave_lds_sync();
-            // 4. one global atomic per distinct cell row and channel, 8 cells
-            //    (x 8 channels) per wave-instruction
-            for (uint32_t j = 0; j < n; j += 8u) {
-                const uint32_t idx = j + (lane >> 3);
-                if (idx < n) {
-                    const uint32_t e = rows[idx];
-                    atomicAdd(base + (size_t)(e >> 6) * 8u, slice[(e & 63u) * 8u + ch]);
+        for (int c = 0; c < 8; ++c) {
+            const float wx = (c & 1) ? fx : 1.0f - fx;
+            const float wy = (c & 2) ? fy : 1.0f - fy;
+            const float wz = (c & 4) ? fz : 1.0f - fz;
+            const uint32_t row = dense_or_hash_row((c & 1) ? nx : cx, (c & 2) ? ny : cy,
+                                                   (c & 4) ? nz : cz, d);
+            float val = ((wx * wy) * wz) * wg;
+            // merge equal rows of the wave's 8 rays over a 3-level butterfly
+            // so one lane per row and channel issues the atomic
+            bool alive = live;
+#pragma unroll
+            for (int sd = 8; sd < 64; sd <<= 1) {
+                const uint32_t orow = __shfl_xor(row, sd);
+                const float oval = __shfl_xor(val, sd);
+                const int oalive = __shfl_xor((int)alive, sd);
+                if (alive && oalive && orow == row) {
+                    if (lane & sd) alive = false;
+                    else val += oval;
                 }
             }
-            wave_lds_sync();                                  // reads done before the next zeroing
-        } else if (run) {
-            uint32_t nrow[8];
-            float nval[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float wx = (c & 1) ? fx : 1.0f - fx;
-                const float wy = (c & 2) ? fy : 1.0f - fy;
-                const float wz = (c & 4) ? fz : 1.0f - fz;
-                nrow[c] = dense_or_hash_row((c & 1) ? nx : cx, (c & 2) ? ny : cy, (c & 4) ? nz : cz, d);
-                nval[c] = ((wx * wy) * wz) * wg;
-            }
-#pragma unroll
-            for (int p = 0; p < 8; ++p) {
-                bool hit = false;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const bool h = !hit && prow[p] == nrow[c];
-                    nval[c] += h ? pval[p] : 0.0f;
-                    hit = hit || h;
-                }
-                if (!hit && live && prow[p] != 0xFFFFFFFFu) atomicAdd(base + (size_t)prow[p] * 8u, pval[p]);
-            }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                prow[c] = nrow[c];
-                pval[c] = nval[c];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float wx = (c & 1) ? fx : 1.0f - fx;
-                const float wy = (c & 2) ? fy : 1.0f - fy;
-                const float wz = (c & 4) ? fz : 1.0f - fz;
-                const uint32_t row = dense_or_hash_row((c & 1) ? nx : cx, (c & 2) ? ny : cy,
-                                                       (c & 4) ? nz : cz, d);
-                float val = ((wx * wy) * wz) * wg;
-                // merge equal rows of the wave's 8 rays over a 3-level butterfly
-                // so one lane per row and channel issues the atomic
-                bool alive = live;
-#pragma unroll
-                for (int sd = 8; sd < 64; sd <<= 1) {
-                    const uint32_t orow = __shfl_xor(row, sd);
-                    const float oval = __shfl_xor(val, sd);
-                    const int oalive = __shfl_xor((int)alive, sd);
-                    if (alive && oalive && orow == row) {
-                        if (lane & sd) alive = false;
-                        else val += oval;
-                    }
-                }
-                if (alive) {
-                    if (DET && fixed)
-                        atomicAdd(dbase + (size_t)row * 8u,
-                                  (unsigned long long)__double2ll_rn((double)val * dscale));
-                    else
-                        atomicAdd(base + (size_t)row * 8u, val);
-                }
+            if (alive) {
+                if (DET && fixed)
+                    atomicAdd(dbase + (size_t)row * 8u,
+                              (unsigned long long)__double2ll_rn((double)val * dscale));
+                else
+                    atomicAdd(base + (size_t)row * 8u, val);
             }
         }
     }
-    if (run && live)
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (prow[c] != 0xFFFFFFFFu) atomicAdd(base + (size_t)prow[c] * 8u, pval[c]);
 }
 
 // max |grad_fsam[ray, 0:128]| into hdr[0] and a non-finite flag into hdr[1]
@@ -620,7 +507,7 @@ int samnerf_sgrid_backward_det(const samnerf_model* m, const float* grad_fsam, u
         return fail(SAMNERF_ELAUNCH, "sgrid_backward_det: header reset failed");
     k_sgrid_det_max<<<div_up((uint64_t)N * 32u, 256), 256, 0, s>>>(grad_fsam, N, kRow, hdr);
     k_sgrid_backward<32, true><<<dim3(div_up((uint64_t)N * 8, 256), 16, 1), 256, 0, s>>>(
-        N, make_ray_tiles(N, m->view_width), gs, w.u_f, w.w_f, grad_fsam, kRow, grad_embeddings, 0u, 0u, det);
+        N, make_ray_tiles(N, m->view_width), gs, w.u_f, w.w_f, grad_fsam, kRow, grad_embeddings, det);
     k_sgrid_det_finish<<<2048, 256, 0, s>>>(det, grad_embeddings, n);
     return check_launch("sgrid_backward_det");
 }
@@ -638,32 +525,9 @@ int samnerf_sgrid_backward(const samnerf_model* m, const float* grad_fsam, uint3
     GridDesc<16> gs;
     int rc = make_grid_desc(m->s_grid, 8, 16, gs, "s_grid");
     if (rc) return rc;
-    for (int l = 0; l < 16; ++l)       // box cells carry row << 6 | cell in 32 bits
-        if (gs.lv[l].size > (1u << 26))
-            return fail(SAMNERF_EINVAL, "sgrid_backward: level %d has more than 2^26 rows", l);
-    // SAMNERF_SGRID_BWD=box: the LDS-box aggregation (A/B and tests; measured
-    // slower than the per-corner atomics, 0.70 vs 0.56 ms per cfg-5 step, so
-    // not the default); SAMNERF_SGRID_BWD_SPLIT: sample groups per ray
-    // (blockIdx.z; 1 = the round-1 form, 4-16 measured no faster)
-    // SAMNERF_SGRID_BWD=run: the along-ray merge on every level
-    // (SAMNERF_SGRID_RUN_RES: up to this level resolution).  Measured slower on
-    // a cfg-5 step: 1.29 ms per step with the per-corner form, 1.62 with the
-    // merge on every level, 1.50 on levels up to res 64 (tools/r2/gpu_r2s3n.sh):
-    // a wave's 8 neighbouring rays share corner rows at one sample index (the
-    // butterfly) more often than consecutive samples of one ray do, and the
-    // merge gives the butterfly up.  Kept selectable and tested.
-    const char* mode = diag_env("SAMNERF_SGRID_BWD");
-    const uint32_t max_cells = (mode && !strcmp(mode, "box")) ? kBwdBoxCells : 0u;
-    const char* rr = diag_env("SAMNERF_SGRID_RUN_RES");
-    uint32_t run_res = rr ? (uint32_t)atoi(rr) : 0u;
-    if (mode && !strcmp(mode, "run") && !rr) run_res = 0xFFFFFFFFu;
-    const char* sp = diag_env("SAMNERF_SGRID_BWD_SPLIT");
-    const uint32_t split = sp ? (uint32_t)std::max(1, std::min(32, atoi(sp))) : 1u;
-    k_sgrid_backward<32><<<dim3(div_up((uint64_t)N * 8, 256), 16, split), 256, 0,
-                           reinterpret_cast<hipStream_t>(stream)>>>(N, make_ray_tiles(N, m->view_width),
-                                                                     gs, w.u_f, w.w_f, grad_fsam,
-                                                                     kRow, grad_embeddings, max_cells,
-                                                                     run_res);
+    k_sgrid_backward<32><<<dim3(div_up((uint64_t)N * 8, 256), 16, 1), 256, 0,
+                           reinterpret_cast<hipStream_t>(stream)>>>(
+        N, make_ray_tiles(N, m->view_width), gs, w.u_f, w.w_f, grad_fsam, kRow, grad_embeddings);
     return check_launch("sgrid_backward");
 }
 

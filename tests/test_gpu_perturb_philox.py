@@ -232,20 +232,3 @@ def test_rgb_train_step_seeded_equals_arrays(hip_lib, cuda):
         assert torch.equal(res[0][2][k], res[1][2][k]), k
     for k, g in res[1][3].items():
         assert float((res[0][3][k] - g).norm() / g.norm().clamp_min(1e-12)) <= GRAD_TOL, k
-
-
-def test_one_kernel_proposal_form_seeded(hip_lib, cuda, monkeypatch):
-    """The diagnostic library's k_prop_fused took the seeded source too:
-    bit-identical to the product's two-kernel form."""
-    from samnerf_amd import _lib
-    from samnerf_amd.fused import FusedRenderer, PhiloxPerturb
-    net = _sam_net(cuda)
-    ro, rd = _view(64, 8, cuda)
-    prod = FusedRenderer(net).render(ro, rd, perturb=PhiloxPerturb(SEED, 6), view_width=64)
-    monkeypatch.setenv("SAMNERF_PROP_FUSED", "1")
-    with _lib.diag_library():
-        one = FusedRenderer(net).render(ro, rd, perturb=PhiloxPerturb(SEED, 6), view_width=64)
-        plain = FusedRenderer(net).render(ro, rd, view_width=64)
-    monkeypatch.delenv("SAMNERF_PROP_FUSED")
-    _same(prod, one, OUTS, "k_prop_fused seeded")
-    assert not torch.equal(plain["image"], one["image"])

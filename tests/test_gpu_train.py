@@ -104,49 +104,6 @@ def test_distillation_step_matches_cpu_twin_full_tables(hip_lib, cuda, det):
     assert len(errs) == 13 and max(errs.values()) < 1e-4, errs
 
 
-def test_sgrid_backward_box_matches_per_corner(hip_lib, cuda, monkeypatch, diag):
-    """The s_grid scatter's LDS-box aggregation (SAMNERF_SGRID_BWD=box; per
-    wave and sample: corner sums in LDS, non-zero cells compacted, one atomic
-    per distinct row) and the along-ray merge (SAMNERF_SGRID_BWD=run: a lane
-    keeps the previous sample's corner rows pending) against the default
-    per-corner form on the full-size table, a
-    64x64 view and a ray set with scattered rays (boxes too big -> per-corner
-    path inside the same launch): equal up to float-atomic order."""
-    from samnerf_amd import ops
-    from samnerf_amd.fused import FusedRenderer, ROW
-    spec = synth.ModelSpec(with_sam=True)
-    net = make_net(spec, synth.make_params(spec, seed=9, emb_scale=0.5, ln_jitter=0.1), cuda)
-    pose, intr = synth.gui_camera(64, 64, rot=synth.random_rotation(14))
-    ro, rd = ops.get_rays(pose, intr, 64, 64, device=cuda)
-    perm = torch.randperm(4096, generator=torch.Generator().manual_seed(1)).to(cuda)
-    ro = torch.cat([ro, ro[perm[:1000]]]).contiguous()
-    rd = torch.cat([rd, rd[perm[:1000]]]).contiguous()
-    N = ro.shape[0]
-    fr = FusedRenderer(net)
-    rows = torch.empty(N, ROW, device=cuda)
-    out = fr.render(ro, rd, rows=rows, keep_workspace=True, feats=False, own_workspace=True)
-    ws = out["_workspace"]
-    g = torch.randn(N, ROW, device=cuda, generator=torch.Generator(device=cuda).manual_seed(2))
-    grads = {}
-    for mode in ("box", "corner", "run"):
-        monkeypatch.setenv("SAMNERF_SGRID_BWD", mode)
-        ge = torch.zeros_like(net.s_grid.embeddings)
-        fr.sgrid_backward(g, ws, ge)
-        grads[mode] = ge
-    b = grads["corner"]
-    for mode in ("box", "run"):
-        a = grads[mode]
-        assert (a != 0).sum() > 10000
-        # another association of the same float sums (LDS first / along the
-        # ray first, then one atomic per row): relative to the tensor, not per
-        # element (rows whose contributions cancel carry no relative precision
-        # in any form)
-        rel = ((a - b).norm() / b.norm()).item()
-        mx = ((a - b).abs().max() / b.abs().max()).item()
-        print(mode, "vs per-corner scatter:", rel, mx)
-        assert rel < 1e-5 and mx < 1e-5, (mode, rel, mx)
-
-
 def test_sgrid_backward_deterministic_mode(hip_lib, cuda):
     """the deterministic s_grid scatter (samnerf_sgrid_backward_det:
     64-bit fixed-point integer atomics, associative) gives the same bits on

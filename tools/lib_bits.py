@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Fingerprints of the outputs of one library build (SAMNERF_LIB, or the
 in-tree product): the headline view on the default and the parity-weight
-scene, the sphere scene, an array-perturbed view, the --with_mask view and one mask-training forward,
-as sha256 prefixes of the raw bytes.  Two builds whose lines match are
+scene, the sphere scene (also under N1 at t_thresh = 1e-4), an array-perturbed
+view, the --with_mask view and one mask-training forward, as sha256 prefixes of the raw bytes.  Two builds whose lines match are
 bit-identical on these workloads (A/B of kernel forms that must keep the
 bits).  usage (GPU box): [SAMNERF_LIB=...] python tools/lib_bits.py"""
 import hashlib
@@ -38,6 +38,10 @@ def main():
             net, _, _ = bench.build_net(True, dev, **kw)
             o = FusedRenderer(net, head_mode=head_mode).render(ro, rd, view_width=W)
             out[f"{tag}_h{head_mode}"] = {k: sha(o[k]) for k in ("image", "depth", "samvit")}
+    # N1, the wave-level early exit (k_final's EXIT forms) on the sphere scene
+    net, _, _ = bench.build_net(True, dev, surface=True, seed=3)
+    o = FusedRenderer(net, t_thresh=1e-4).render(ro, rd, view_width=W)
+    out["sphere_n1"] = {k: sha(o[k]) for k in ("image", "depth", "samvit", "weights_sum")}
     # the array-perturbed render (samnerf_model.perturb): torch's draws from a fixed seed
     from samnerf_amd.fused import perturbed_positions
     net, _, _ = bench.build_net(True, dev, emb_scale=0.5)
