@@ -422,8 +422,14 @@ int samnerf_sgrid_backward(const samnerf_model* model, const float* grad_fsam, u
  * contribution is added to a 64-bit fixed-point accumulator instead (integer
  * atomics are associative: the totals do not depend on the order the waves
  * reach a row in), at the scale 2^(61 - ceil(log2 N) - e) with max |grad_fsam|
- * < 2^e, so no total can overflow and each is resolved to max|g| 2^-(61 -
- * ceil(log2 N)); then the totals are added to grad_embeddings as fp32.
+ * < 2^e, so no total can overflow (the final samples' weights sum to at most
+ * 1 per ray); then the totals are added to grad_embeddings as fp32.  Each
+ * contribution is an fp32 value (its products and the wave's 8-ray merge
+ * round as in the default form) rounded to the quantum 2^(e + ceil(log2 N)
+ * - 61) <= 2 max|g| 2^-(61 - ceil(log2 N)): a total of n contributions is
+ * within n / 2 quanta plus 11 fp32 roundings of sum |contribution| of the
+ * exact sum -- no term grows with n in fp32, which the default form's n
+ * atomic adds have (tests/sgrid_ref.py bound_scatter_det, checked per row).
  * accum: accum_bytes >= samnerf_sgrid_accum_size(model) bytes of device
  * memory (else SAMNERF_EWORKSPACE), all zero on the first call (hipMemset)
  * and left zero by every call; one accumulator per stream (calls on one

@@ -51,6 +51,26 @@ def test_fused_sgrid_backward_matches_autograd(hip_lib, cuda):
         scale = b.abs().max().item()
         assert err <= 2e-3 * max(scale, 1e-3), f"{k}: {err} vs scale {scale}"
 
+    # the scatter alone on this view's own samples, row by row against the
+    # float64 reference at the bound derived from its operations
+    # (tests/sgrid_ref.py; test_gpu_sgrid_scatter.py has the small and ragged N)
+    import grid_ref
+    import sgrid_ref
+    from samnerf_amd.fused import ROW
+    fr = FusedRenderer(net)
+    out = fr.render(ro, rd, rows=torch.empty(32 * 32, ROW, device=cuda), taps=True, keep_workspace=True,
+                    own_workspace=True, feats=False)
+    g = torch.randn(32 * 32, ROW, device=cuda, generator=torch.Generator(device=cuda).manual_seed(6))
+    ge = torch.zeros_like(net.s_grid.embeddings)
+    fr.sgrid_backward(g, out["_workspace"], ge)
+    val, abs_w, abs_1, count = sgrid_ref.scatter(out["u2"].cpu().numpy(), out["w2"].cpu().numpy(),
+                                                 g.cpu().numpy(),
+                                                 synth.ModelSpec(s_grid_log2=14).s_grid)   # _frozen_net's
+    bound = sgrid_ref.bound_scatter_atomic(abs_w, count, float(g[:, :128].abs().max()))
+    ratio = grid_ref.worst_ratio(ge.cpu().numpy(), val, bound, abs_1)
+    print("s_grid scatter, 32x32 view: worst ratio to the derived bound", ratio, "max count", int(count.max()))
+    assert ratio <= 1.0
+
 
 @pytest.mark.parametrize("det", [False, True])
 def test_distillation_step_matches_cpu_twin_full_tables(hip_lib, cuda, det):
