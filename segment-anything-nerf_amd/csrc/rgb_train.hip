@@ -532,11 +532,14 @@ __global__ void __launch_bounds__(256) k_rt_final_bwd_ray_h(RtArgs a) {
     const float e = expf(-ds), Tk = expf(-(float)cum);
     const float raw = (1.0f - e) * Tk;
     const float w = nan_to_num(raw);
-    g = __builtin_fmaf(gdep, a.tmid[s], g);
+    // g so far is the same for every sample of the ray and cancels in the
+    // reverse scan below; what varies with k is summed on its own (gv) and
+    // meets it in double, so that it is not rounded at the constant's scale
+    float gv = gdep * a.tmid[s];
 #pragma unroll
     for (int j = 0; j < 15; ++j) {
         const size_t q = (size_t)(1 + j) * S + s;
-        g = __builtin_fmaf(dfi[j], a.out[q], g);
+        gv = __builtin_fmaf(dfi[j], a.out[q], gv);
         a.dout[q] = w * dfi[j];
     }
     if (c_dist != 0.0f) {
@@ -550,20 +553,26 @@ __global__ void __launch_bounds__(256) k_rt_final_bwd_ray_h(RtArgs a) {
         const double Wt = __shfl(Wi, 31, 32), WMt = __shfl(WMi, 31, 32);
         const double before = md * (Wi - wd) - (WMi - wmd);
         const double after = (WMt - WMi) - md * (Wt - Wi);
-        g = __builtin_fmaf(c_dist, (float)(2.0 * (before + after)) + (2.0f / 3.0f) * iv * w, g);
+        gv = __builtin_fmaf(c_dist, (float)(2.0 * (before + after)) + (2.0f / 3.0f) * iv * w, gv);
     }
-    if (a.g_w) g = g + a.g_w[(size_t)r * kT + k];          // a loss on results['weights'] itself
+    if (a.g_w) gv = gv + a.g_w[(size_t)r * kT + k];        // a loss on results['weights'] itself
     const bool fin = isfinite(raw);                        // nan_to_num_ backward
-    const float dw = fin ? g : 0.0f;
+    const double dw = fin ? (double)g + (double)gv : 0.0;
     // sum_{j>k} dw_j raw_j: the exclusive suffix sum in double (ATen sums the
     // backward of the compositing cumsum in double on the CPU; in fp32, with
     // the inclusive sum minus the own term, the cancellation below lost ~1e-2
-    // of the density gradients against a float64 twin)
-    const double drd = fin ? (double)(dw * raw) : 0.0;
+    // of the density gradients against a float64 twin).  The transmittance
+    // and alpha under it in double too: a part of dw that is the same for
+    // every sample of the ray (d weights_sum, the SH block of f_image) must
+    // cancel in e_k T_k - sum_{j>k} alpha_j T_j = 0, and with expf's rounding
+    // in each factor it left 1e-5 of the image gradient as noise
+    // ('last_sample': weights_sum = 1 has no gradient at all).
+    const double ed = exp(-(double)ds), Td = exp(-cum);
+    const double drd = fin ? dw * ((1.0 - ed) * Td) : 0.0;
     const double after_k = half_incl_suffix(drd, k) - drd;
     float dx = 0.0f;
     if (!inf) {                                            // transparent: the last sample too (after_k = 0)
-        const float dds = (float)((double)(dw * (e * Tk)) - after_k);
+        const float dds = (float)(dw * (ed * Td) - after_k);
         const float x = a.out[s];
         dx = (dds * a.delta[s]) * expf(fminf(fmaxf(x, -15.0f), 15.0f));   // trunc_exp backward
     }
@@ -855,6 +864,7 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
     wave_lds_sync();
     // the 32 final intervals (renderer.py:40-49)
     float loss = 0.0f;
+    int top = 0;                                           // one past the last stage sample an active interval covers
     if (lane < (uint32_t)kT) {
         const uint32_t i = lane;
         const float t0lo = a.bins2[(size_t)i * N + r], t0hi = a.bins2[(size_t)(i + 1) * N + r];
@@ -871,8 +881,11 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
             const float g = -2.0f * x / den * a.c_prop;
             atomicAdd(dd + lo, g);
             atomicAdd(dd + hi + 1, -g);
+            top = hi + 1;
         }
     }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) top = max(top, __shfl_xor(top, m));
     loss = wave_sum(loss);
     wave_lds_sync();
     if (lane == 0) a.terms[N + r] += loss / (float)kT;
@@ -902,7 +915,10 @@ __global__ void __launch_bounds__(256) k_rt_prop_ray_w(PropBwdArgs a) {
         const float ex = expf(-ds), Tj = expf(-(float)cpre);
         cpre += lane * E + e == T - 1 ? 0.0 : (double)ds;
         const float rw = (1.0f - ex) * Tj;
-        const float dw = isfinite(rw) ? dpre : 0.0f;
+        // past the last covered sample every +g has met its -g: the prefix is
+        // zero there, not the fp32 scan's rounding residue (which kept rows
+        // behind a surface from the scatter's zero-wave skip)
+        const float dw = isfinite(rw) && (int)(lane * E + e) < top ? dpre : 0.0f;
         raw[e] = isfinite(rw) ? dw * rw : 0.0f;
         ev[e] = dw * (ex * Tj);
         tail += raw[e];

@@ -5,6 +5,7 @@ reference's unfused autograd graph (run_torch: torch ops + drop-in grid
 backward kernel), and a few Adam steps must reduce the loss
 (nerf/utils.py:1072-1106, main.py:255-262, :296).
 """
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -435,6 +436,155 @@ def test_fused_adam_matches_torch_adam(hip_lib, cuda, wd):
             x, y = o1.state[a][k], o2.state[b][k]
             assert (x - y).abs().max().item() <= 1e-5 * y.abs().max().item(), k
         assert int(o1.state[a]["step"]) == int(o2.state[b]["step"])
+
+
+# --- samnerf_adam_step against a float64 restatement, element by element ---
+_U = 2.0 ** -24                                            # fp32 unit roundoff
+
+
+def _adam_hyper(lr, b1, b2, eps, wd, t):
+    """The scalars of train_optim.hip's AdamHyper: formed in double from the
+    Python values, rounded to float once (math.pow is the C library's pow, as
+    std::pow there); returned as the doubles those floats are."""
+    import math
+    f = lambda x: float(np.float32(x))
+    return dict(w1=f(1.0 - b1), beta2=f(b2), omb2=f(1.0 - b2), bc2_sqrt=f(math.sqrt(1.0 - math.pow(b2, float(t)))),
+                eps=f(eps), step_size=f(-lr / (1.0 - math.pow(b1, float(t)))), wd=f(wd))
+
+
+def _adam_step64(p, g, m, v, h):
+    """One update in float64 from fp32 inputs, the arithmetic the header of
+    train_optim.hip documents, and per element the absolute error an fp32
+    evaluation of it may carry, to first order in u = 2^-24 (every fp32
+    operation, the correctly rounded division and sqrtf included, is off by
+    at most u of its result; an FMA contraction only removes a rounding):
+      g' = g + wd p           u (|wd p| + |g'|)                     (wd != 0)
+      m' = m + w1 (g' - m)    w1 e_g + 2 u w1 |g' - m| + u |m'|
+      v' = v b2 + (c g') g'   u |v b2| + 2 u c g'^2 + 2 c |g'| e_g + u |v'|
+      s  = sqrt(v')           e_v / (2 s) + u s
+      q  = s / bc + eps       e_s / bc + u s / bc + u q
+      r  = m' / q             e_m / q + |m'| e_q / q^2 + u |r|
+      p' = p + step r         |step| e_r + u |step r| + u |p'|
+    about ten roundings; the neglected second-order terms are below 1e-5 of
+    the bound, which is widened by 1e-3.  -> (p', m', v'), (e_p, e_m, e_v)."""
+    p, g, m, v = (np.asarray(x, np.float64) for x in (p, g, m, v))
+    g1, eg = g, np.zeros_like(g)
+    if h["wd"] != 0.0:
+        g1 = g + h["wd"] * p
+        eg = _U * (np.abs(h["wd"] * p) + np.abs(g1))
+    d = g1 - m
+    m1 = m + h["w1"] * d
+    em = h["w1"] * eg + 2 * _U * h["w1"] * np.abs(d) + _U * np.abs(m1)
+    vb, gg = v * h["beta2"], h["omb2"] * g1 * g1
+    v1 = vb + gg
+    ev = _U * np.abs(vb) + 2 * _U * gg + 2 * h["omb2"] * np.abs(g1) * eg + _U * np.abs(v1)
+    s = np.sqrt(v1)
+    es = np.divide(ev, 2 * s, out=np.zeros_like(s), where=s > 0) + _U * s
+    q = s / h["bc2_sqrt"] + h["eps"]
+    eq = es / h["bc2_sqrt"] + _U * s / h["bc2_sqrt"] + _U * q
+    r = m1 / q
+    er = em / q + np.abs(m1) * eq / (q * q) + _U * np.abs(r)
+    p1 = p + h["step_size"] * r
+    ep = abs(h["step_size"]) * er + _U * np.abs(h["step_size"] * r) + _U * np.abs(p1)
+    return (p1, m1, v1), tuple(1.001 * e for e in (ep, em, ev))
+
+
+def _adam_tensors(cuda, seed):
+    """40 parameters of one group -- three passes of samnerf_adam_step's
+    16-tensor table -- with the sizes at which k_adam takes another path:
+    4,096 / 4,100 / 8,192 (16-B vectors: one block exactly, one block and a
+    4-element tail, two blocks), 4,097 / 12,289 (n % 4 != 0: the scalar path
+    over two and four blocks, ragged), 3, a contiguous view one float into its
+    storage (n % 4 == 0 but only 4-B aligned: the scalar path) between two
+    sentinels, and small 2-D shapes for the rest.  -> (params, storage of the
+    misaligned one, its index)."""
+    g = torch.Generator().manual_seed(seed)
+    sizes = {3: (4096,), 7: (4100,), 12: (8192,), 15: (4097,), 16: (12289,), 21: (3,), 33: (1,)}
+    params = []
+    for j in range(40):
+        shape = sizes.get(j, (1 + j % 5, 4 + j % 3))
+        params.append(torch.nn.Parameter(torch.randn(*shape, generator=g).to(cuda)))
+    store = torch.randn(4100 + 2, generator=g).to(cuda)
+    off = 30
+    params[off] = torch.nn.Parameter(store[1:4101])          # shares the storage: data_ptr() = base + 4
+    assert params[off].data_ptr() % 16 == 4 and params[off].is_contiguous() and params[off].numel() % 4 == 0
+    return params, store, off
+
+
+@pytest.mark.parametrize("wd", [0.0, 1e-3])
+def test_fused_adam_vs_float64_per_element(hip_lib, cuda, wd):
+    """Three FusedAdam steps over _adam_tensors: after each step every element
+    of every parameter, exp_avg and exp_avg_sq is within _adam_step64's bound
+    of the float64 update of the kernel's own previous state -- so each of the
+    40 tensors is updated exactly once per step (a second update, or none,
+    misses the bound by orders of magnitude).  Gradients are scaled 1e-6, 1e-3,
+    1 and 1e3 by tensor.  Parameter 18 has no gradient, in the middle of the
+    second table: it keeps its bits and gets no state; the floats before and
+    after the misaligned view keep theirs."""
+    from samnerf_amd.optim import FusedAdam
+    params, store, off = _adam_tensors(cuda, 7)
+    no_grad = 18
+    lr, betas, eps = 1e-2, (0.9, 0.999), 1e-15
+    opt = FusedAdam(params, lr=lr, betas=betas, eps=eps, weight_decay=wd)
+    sentinels = (store[0].item(), store[-1].item())
+    frozen = params[no_grad].detach().cpu().numpy().copy()
+    g = torch.Generator().manual_seed(11)
+    worst = {"param": 0.0, "exp_avg": 0.0, "exp_avg_sq": 0.0}
+    for t in (1, 2, 3):
+        before = []
+        for j, p in enumerate(params):
+            st = opt.state.get(p, {})
+            zeros = np.zeros(tuple(p.shape), np.float32)
+            before.append((p.detach().cpu().numpy().copy(),
+                           st["exp_avg"].cpu().numpy().copy() if st else zeros,
+                           st["exp_avg_sq"].cpu().numpy().copy() if st else zeros))
+            p.grad = None if j == no_grad else \
+                (torch.randn(p.shape, generator=g) * 10.0 ** (3 * (j % 4) - 6)).to(cuda)
+        opt.step()
+        torch.cuda.synchronize()
+        h = _adam_hyper(lr, betas[0], betas[1], eps, wd, t)
+        for j, p in enumerate(params):
+            if j == no_grad:
+                continue
+            want, bound = _adam_step64(before[j][0], p.grad.cpu().numpy(), before[j][1], before[j][2], h)
+            got = (p.detach(), opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])
+            for name, x, w, b in zip(worst, got, want, bound):
+                x = x.cpu().numpy()
+                assert x.dtype == np.float32 and np.isfinite(x).all(), (t, j, name)
+                err = np.abs(x.astype(np.float64) - w)
+                assert (err[b == 0] == 0).all(), (t, j, name)
+                ratio = float((err[b > 0] / b[b > 0]).max()) if (b > 0).any() else 0.0
+                assert ratio <= 1.0, (f"step {t} tensor {j} {tuple(p.shape)} {name}: {ratio:.3f} of the bound at "
+                                      f"element {int(np.argmax(np.where(b > 0, err / np.where(b > 0, b, 1), 0)))}")
+                worst[name] = max(worst[name], ratio)
+            assert int(opt.state[p]["step"]) == t
+        assert np.array_equal(params[no_grad].detach().cpu().numpy().view(np.uint32), frozen.view(np.uint32))
+        assert params[no_grad] not in opt.state
+        assert (store[0].item(), store[-1].item()) == sentinels
+    print(f"adam_ratio wd={wd} " + " ".join(f"{k}={v:.3f}" for k, v in worst.items()))
+
+
+def test_fused_adam_misaligned_gradient_and_state(hip_lib, cuda):
+    """16-B alignment is asked of all four buffers: a gradient that starts one
+    float into its storage (the parameter and the state aligned, n % 4 == 0)
+    takes the scalar path too, within the same bound, over more than one
+    block."""
+    from samnerf_amd.optim import FusedAdam
+    g = torch.Generator().manual_seed(5)
+    p = torch.nn.Parameter(torch.randn(8192, generator=g).to(cuda))
+    gstore = torch.randn(8194, generator=g).to(cuda)
+    keep = gstore.clone()
+    opt = FusedAdam([p], lr=1e-2, eps=1e-15)
+    p0 = p.detach().cpu().numpy().copy()
+    p.grad = gstore[1:8193]
+    assert p.grad.data_ptr() % 16 == 4 and p.grad.is_contiguous()
+    opt.step()
+    torch.cuda.synchronize()
+    assert torch.equal(gstore, keep)
+    z = np.zeros(8192, np.float32)
+    want, bound = _adam_step64(p0, keep[1:8193].cpu().numpy(), z, z, _adam_hyper(1e-2, 0.9, 0.999, 1e-15, 0.0, 1))
+    for x, w, b in zip((p.detach(), opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"]), want, bound):
+        assert (np.abs(x.cpu().numpy().astype(np.float64) - w) <= b).all()
 
 
 
