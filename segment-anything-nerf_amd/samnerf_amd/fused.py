@@ -5,8 +5,19 @@ nerf/network.py, or anything exposing the same attributes / state_dict keys)
 and renders rays with the whole NeRFRenderer.run loop
 (nerf/renderer.py:221-390) in five kernel launches.  Parameters are read in
 place (torch layout); nothing is copied or cached between calls except the
-workspace buffer.
+scratch buffers (one per kind, device and stream).
+
+Per-call state: `FusedRenderer.model()` is the cached samnerf_model of the
+network, never written after it is built.  Every C call takes a fresh copy of
+it with that call's view_width / with_mask / perturb / reuse_packed
+(`call_model`), which carries the host arrays and perturb tensors it points
+at; an autograd context keeps its forward's copy and hands it to the backward
+unchanged.  The library's own per-thread state (background, parity taps) is
+set for the C calls of one `call_scope` and restored when it exits.  So
+renders on one renderer from several threads, each on its own stream, share
+nothing that a call writes.
 """
+import contextlib
 import ctypes
 import dataclasses
 
@@ -81,16 +92,79 @@ class PhiloxPerturb:
                 raise ValueError(f"PhiloxPerturb: {name} must be an integer in [0, 2^64)")
 
 
-def set_perturb(m, pert):
-    """Point the samnerf_model struct `m` at one perturb source for a call: None
-    (perturb=False), a PhiloxPerturb, or the (bins0, u1, u2) tensors; the caller
-    keeps the tensors alive and calls set_perturb(m, None) afterwards."""
-    seeded = isinstance(pert, PhiloxPerturb)
-    m.perturb_device = int(seeded)
-    m.perturb_seed = pert.seed if seeded else 0
-    m.perturb_offset = pert.offset if seeded else 0
+def resolve_perturb(perturb, N, num_steps, device):
+    """A caller's perturb= for a call over N rays as what call_model takes:
+    None (False, 0, None), the PhiloxPerturb itself, or the three contiguous
+    fp32 arrays (bins0 [N, T0+1], u1 [N, T1+1], u2 [N, T2+1]) -- the caller's
+    tuple or list, or perturbed_positions' draw for True and for the GUI's spp
+    (an int).  Arrays of any other count or shape are a ValueError."""
+    if isinstance(perturb, PhiloxPerturb):
+        return perturb
+    given = isinstance(perturb, (tuple, list))
+    if not given and not perturb:
+        return None
+    steps = [int(v) for v in num_steps]
+    pert = tuple(perturb) if given else perturbed_positions(N, steps, device)
+    shapes = [(N, T + 1) for T in steps]
+    if len(pert) != 3 or any(tuple(t.shape) != sh for t, sh in zip(pert, shapes)):
+        raise ValueError(f"fused render: perturb arrays must have shapes {shapes}")
+    if any(t.device != torch.device(device) for t in pert):
+        raise RuntimeError(f"fused render: perturb arrays must be on {device}")
+    return tuple(t.contiguous().float() for t in pert)
+
+
+def call_model(base, *, view_width=0, with_mask=0, perturb=None, reuse_packed=0):
+    """The samnerf_model of one C call: a copy of `base` (FusedRenderer.model(),
+    whose per-call fields are zero / NULL) with that call's view_width,
+    with_mask, reuse_packed and perturb source -- resolve_perturb's None, a
+    PhiloxPerturb (drawn in the kernels: no arrays) or the three arrays.  The
+    copy's `keep` list holds what its pointers need alive beyond the network's
+    parameters: the base's host arrays and the perturb tensors.  `base` is
+    not written."""
+    m = SamnerfModel.from_buffer_copy(base)
+    m.keep = list(base.keep)
+    m.view_width = int(view_width or 0)
+    m.with_mask = int(with_mask)
+    m.reuse_packed = int(reuse_packed)
+    if isinstance(perturb, PhiloxPerturb):
+        m.perturb_device, m.perturb_seed, m.perturb_offset = 1, perturb.seed, perturb.offset
+    elif perturb is not None:
+        for i, t in enumerate(perturb):
+            if not (t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError(f"fused render: perturb[{i}] must be a contiguous float32 tensor")
+            m.perturb[i] = ctypes.c_void_p(t.data_ptr())
+        m.keep.extend(perturb)
+    return m
+
+
+def rgb_grads_struct(tensors, with_prop):
+    """samnerf_rgb_grads pointing at `tensors`, the gradient buffers in
+    rgb_train_params order; without with_prop the proposal networks' pointers
+    stay NULL (the kernels then write none)."""
+    g = SamnerfRgbGrads()
+    g.grid = tensors[0].data_ptr()
     for i in range(3):
-        m.perturb[i] = None if (pert is None or seeded) else _param(pert[i], f"perturb[{i}]")
+        g.grid_mlp[i] = tensors[1 + i].data_ptr()
+        g.view_mlp[i] = tensors[4 + i].data_ptr()
+    if with_prop:
+        g.prop[0], g.prop[1] = tensors[7].data_ptr(), tensors[8].data_ptr()
+        for q in range(2):
+            for i in range(2):
+                g.prop_mlp[q][i] = tensors[9 + 2 * q + i].data_ptr()
+    return g
+
+
+def pack_key(library, ws, m, tensors):
+    """What the packed weights a render leaves in workspace `ws` depend on: the
+    library handle that packed (the diagnostic build has layouts of its own),
+    the buffer, head_mode / with_sam, and the packed tensors (grid_mlp, the SAM
+    head's weights) as (data pointer, torch version counter) -- an in-place
+    update (optimizer step, copy_, load_state_dict, FusedAdam) bumps the
+    counter, a new tensor changes the pointer; `.data` writes do not
+    (FusedRenderer.invalidate_packed).  The packed regions lead the workspace
+    (raymarch.hip carve()): their place does not depend on N."""
+    return (id(library), ws.data_ptr(), int(m.head_mode), int(m.with_sam),
+            tuple((t.data_ptr(), t._version) for t in tensors))
 
 
 def bg_layout(bg_color, N):
@@ -144,8 +218,8 @@ def set_background(net, rows):
     """samnerf_set_background for the next calls of this thread: the network's
     compositing mode and the background colours of one call (background_rows'
     tensor, kept alive by the caller; None: the scalar argument).
-    set_background(None, None) restores the library's defaults -- callers do
-    that in a finally, as for the perturb pointers."""
+    set_background(None, None) restores the library's defaults (call_scope
+    does both)."""
     # (an older build loaded through SAMNERF_LIB for an A/B has no setter: it
     # knows the defaults only)
     setter = getattr(lib(), "samnerf_set_background", None)
@@ -162,6 +236,23 @@ def set_background(net, rows):
     b.bg_rgb = None if rows is None else ctypes.c_void_p(rows.data_ptr())
     b.n_bg = 0 if rows is None else int(rows.shape[0])
     check(setter(ctypes.byref(b)), "set_background")
+
+
+@contextlib.contextmanager
+def call_scope(net, bg_rows, taps=None, N=0):
+    """The library's per-thread state for the C calls made inside the block:
+    the network's background mode with one call's colour rows (set_background)
+    and, optionally, the parity taps (a SamnerfTaps over N rays).  The
+    defaults are back when the block exits, however it exits."""
+    try:
+        set_background(net, bg_rows)
+        if taps is not None:
+            check(lib().samnerf_set_taps(ctypes.byref(taps), N), "set_taps")
+        yield
+    finally:
+        if taps is not None:
+            lib().samnerf_set_taps(None, 0)
+        set_background(None, None)
 
 
 def _steps3(num_steps):
@@ -207,6 +298,65 @@ def ray_of_slots(N, view_width):
     return (trow * 4 + (inn >> 3)) * W + tcol * 8 + (inn & 7)
 
 
+def _render_outputs(N, dev, head, out_tile, mask, bg_rows):
+    """(image, depth, weights_sum, samvit or None) of a render: fresh tensors,
+    or views of the caller's out_tile after checking it (render's docstring);
+    head: the render computes the SAM features."""
+    if out_tile is None:
+        return (torch.empty(N, 3, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev),
+                torch.empty(N, 256, device=dev) if head else None)
+    if bg_rows is not None and bg_rows.shape[0] != 1:
+        raise NotImplementedError("fused render: a per-ray background with out_tile (a sharded view "
+                                  "takes a scalar or one colour)")
+    need_c = 261 if head else 5
+    if (out_tile.dim() != 2 or out_tile.shape[0] != N or out_tile.shape[1] < need_c
+            or out_tile.dtype != torch.float32 or not out_tile.is_contiguous() or out_tile.device != dev):
+        raise ValueError(f"fused render: out_tile must be a contiguous fp32 [{N}, >={need_c}] tensor on {dev}")
+    if mask:
+        raise NotImplementedError("fused render: out_tile with mask outputs")
+    return out_tile[:, 0:3], out_tile[:, 3], out_tile[:, 4], out_tile[:, 5:261] if head else None
+
+
+def _alloc_taps(num_steps, N, taps, dev):
+    """The parity-tap buffers of a render over N rays (render's taps=True, or
+    the row stride): (SamnerfTaps pointing at them, the sample-major per-sample
+    buffers by name, the corner-row buffers by name, the stride)."""
+    steps = [int(v) for v in num_steps]
+    stride = 61 if taps is True else int(taps)
+    n_tap = (N + stride - 1) // stride
+    tap = {"ds0": torch.empty(steps[0], N, device=dev), "ds1": torch.empty(steps[1], N, device=dev),
+           "w0": torch.empty(steps[0], N, device=dev), "w1": torch.empty(steps[1], N, device=dev),
+           "bins1": torch.empty(steps[1] + 1, N, device=dev),
+           "bins2": torch.empty(steps[2] + 1, N, device=dev),
+           "inds1": torch.empty(steps[1] + 1, N, device=dev, dtype=torch.int32),
+           "inds2": torch.empty(steps[2] + 1, N, device=dev, dtype=torch.int32),
+           "sigma2": torch.empty(steps[2], N, device=dev), "w2": torch.empty(steps[2], N, device=dev),
+           "u2": torch.empty(steps[2], 3, N, device=dev)}
+    rows_tap = {"rows2": torch.full((n_tap, steps[2], 16, 8), -1, device=dev, dtype=torch.int32),
+                "srows": torch.full((n_tap, steps[2], 16, 8), -1, device=dev, dtype=torch.int32)}
+    st = SamnerfTaps(*[t.data_ptr() for t in tap.values()], stride,
+                     rows_tap["rows2"].data_ptr(), rows_tap["srows"].data_ptr())
+    return st, tap, rows_tap, stride
+
+
+def _taps_in_ray_order(taps, N, view_width, dev):
+    """The tap entries of render's dict from _alloc_taps' buffers after the
+    call: the kernels keep per-sample intermediates in slot order (ray tiling,
+    samnerf_model.view_width), so they go back to ray order here; the corner
+    rows stay per slot, with tap_rays naming their rays."""
+    _, tap, rows_tap, stride = taps
+    ray_of = ray_of_slots(N, view_width).to(dev)
+    out = {}
+    for k, v in tap.items():
+        v = v.permute(2, 0, 1) if k == "u2" else v.t()
+        r = torch.empty_like(v)
+        r[ray_of] = v
+        out[k] = r
+    out.update(rows_tap)
+    out["tap_rays"] = ray_of[torch.arange(0, N, stride, device=dev)].cpu()
+    return out
+
+
 def last_forms():
     """The compiled kernel forms the calling thread's last render launched
     (samnerf_last_forms): [prop0 level classes, prop1 level classes, k_final
@@ -232,13 +382,10 @@ class FusedRenderer:
         reference's unordered fp32 atomics."""
         self.net = net
         self.deterministic = bool(deterministic)
-        self._accum = None
-        self._ws = None
+        self._buffers = {}     # (kind, device, stream) -> scratch buffer (_scratch)
         self._packed = {}      # (device, stream) -> what its workspace's packed weights are
         self.last_reuse_packed = 0
-        self._keep = []
-        self._model = None
-        self._model_key_cached = None
+        self._model = None     # (_model_key, the base struct)
         self._head_mode = head_mode
         self._t_thresh = None if t_thresh is None else float(t_thresh)
         if not 0.0 <= self.t_thresh < 1.0:
@@ -255,9 +402,10 @@ class FusedRenderer:
         return float(self._t_thresh if self._t_thresh is not None else getattr(self.net, "t_thresh", 0.0))
 
     # --------------------------------------------------------------- model --
-    def _grid(self, enc, name):
+    @staticmethod
+    def _grid(enc, name, keep):
         offs = np.ascontiguousarray(enc.offsets_host, np.int32)
-        self._keep.append(offs)
+        keep.append(offs)
         g = SamnerfGrid()
         g.embeddings = _param(enc.embeddings, name + ".embeddings")
         g.offsets_host = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
@@ -278,24 +426,29 @@ class FusedRenderer:
                 float(n.opt.min_near), float(n.bound), bool(n.opt.with_sam))
 
     def model(self):
-        """The samnerf_model struct of the wrapped network, rebuilt only when
-        _model_key changes: reading the aabb back to the host would otherwise
-        synchronise the stream on every call and stall the launch queue."""
+        """The base samnerf_model struct of the wrapped network, rebuilt only
+        when _model_key changes: reading the aabb back to the host would
+        otherwise synchronise the stream on every call and stall the launch
+        queue.  Read-only: its per-call fields stay zero / NULL, and a C call
+        takes call_model()'s copy, never this struct."""
         key = self._model_key()
-        if self._model is not None and key == self._model_key_cached:
-            return self._model
-        self._model = self._build_model()
-        self._model_key_cached = key
-        return self._model
+        cached = self._model
+        if cached is None or cached[0] != key:
+            cached = self._model = (key, self._build_model())
+        return cached[1]
+
+    def call_model(self, **per_call):
+        """A fresh struct for one C call: the module's call_model on model()."""
+        return call_model(self.model(), **per_call)
 
     def _build_model(self):
         n = self.net
         opt = n.opt
-        self._keep = []
         m = SamnerfModel()
-        m.grid = self._grid(n.grid, "grid")
-        m.prop[0] = self._grid(n.prop_encoders[0], "prop_encoders.0")
-        m.prop[1] = self._grid(n.prop_encoders[1], "prop_encoders.1")
+        keep = m.keep = []                              # the grids' host offset arrays
+        m.grid = self._grid(n.grid, "grid", keep)
+        m.prop[0] = self._grid(n.prop_encoders[0], "prop_encoders.0", keep)
+        m.prop[1] = self._grid(n.prop_encoders[1], "prop_encoders.1", keep)
         for i in range(3):
             m.grid_mlp[i] = _param(n.grid_mlp.net[i].weight, f"grid_mlp.net.{i}.weight")
             m.view_mlp[i] = _param(n.view_mlp.net[i].weight, f"view_mlp.net.{i}.weight")
@@ -304,7 +457,7 @@ class FusedRenderer:
                 m.prop_mlp[p][i] = _param(n.prop_mlp[p].net[i].weight, f"prop_mlp.{p}.net.{i}.weight")
         m.with_sam = int(bool(opt.with_sam))
         if opt.with_sam:
-            m.s_grid = self._grid(n.s_grid, "s_grid")
+            m.s_grid = self._grid(n.s_grid, "s_grid", keep)
             skip = n.samvit_mlp[0]
             for i in range(5):
                 m.sam_w[i] = _param(skip.net[i].weight, f"samvit_mlp.0.net.{i}.weight")
@@ -322,7 +475,7 @@ class FusedRenderer:
         m.t_thresh = float(self.t_thresh)
         kind = mask_kind(n)
         if kind == 0:                                   # --with_mask, mask_mlp_type 'default'
-            m.m_grid = self._grid(n.m_grid, "m_grid")
+            m.m_grid = self._grid(n.m_grid, "m_grid", keep)
             skip = n.mask_mlp[0]
             for i in range(3):
                 m.mask_w[i] = _param(skip.net[i].weight, f"mask_mlp.0.net.{i}.weight")
@@ -332,42 +485,66 @@ class FusedRenderer:
                 m.mask_w[i] = _param(lin.weight, f"mask_mlp.{i}.weight")
             m.mask_out = int(n.mask_mlp[-1].weight.shape[0])
         m.mask_kind = kind or 0
-        m.with_mask = 0                                 # set per call (render(mask=True))
         m.sum_after_mlp = int(bool(getattr(opt, "sum_after_mlp", False)))
         return m
 
     def invalidate_packed(self):
         """Forget the packed weights of every workspace: call after changing
         grid_mlp or SAM-head weights in a way torch's version counter does not
-        see (writes through `.data`, or through raw pointers from C)."""
+        see (writes through `.data`, or through raw pointers from C).  The
+        usual case is an EMA swap around evaluation, the reference Trainer's
+        torch_ema pattern `ema.store(); ema.copy_to()` ... `ema.restore()`:
+        copy_to and restore write through `param.data`, so a render after
+        either would reuse the weights packed before it -- call this after
+        copy_to() and again after restore()."""
         self._packed = {}
 
-    def _pack_signature(self, m):
-        """What the packed weights of a render depend on: head_mode and the
-        packed tensors (grid_mlp, the SAM head's weights) as (data pointer,
-        torch version counter) -- an in-place update (optimizer step, copy_,
-        load_state_dict, FusedAdam) bumps the counter, a new tensor changes
-        the pointer; `.data` writes do not (invalidate_packed)."""
+    def _packed_tensors(self, m):
+        """The tensors a render packs into its workspace (pack_key)."""
         n = self.net
         ts = [n.grid_mlp.net[i].weight for i in range(3)]
         if m.with_sam:
             ts += [n.samvit_mlp[0].net[i].weight for i in range(5)]
-        # (the packed regions lead the workspace, raymarch.hip carve(): their
-        # place does not depend on N; the model fields before them are here)
-        return (int(m.head_mode), int(m.with_sam), tuple((t.data_ptr(), t._version) for t in ts))
+        return ts
+
+    def _scratch(self, kind, device, nbytes, zero=False):
+        """The renderer's scratch buffer of one kind ("render", "accum",
+        "rgb_train"), at least nbytes long, one per (kind, device, current
+        stream): calls on one stream reuse it in stream order, calls issued on
+        different streams (concurrent views) never share one.  zero=True: new
+        buffers are zero-filled (an accumulator every call leaves zero)."""
+        key = (kind, device, _stream_key(device))
+        buf = self._buffers.get(key)
+        if buf is None or buf.numel() < nbytes:
+            new = torch.zeros if zero else torch.empty
+            buf = self._buffers[key] = new(max(nbytes, 1), dtype=torch.uint8, device=device)
+        return buf
+
+    @property
+    def _accum(self):
+        """The "accum" scratch buffers by (device, stream): a read-only view
+        for the tests that look up the one accumulator of a single stream."""
+        return {k[1:]: b for k, b in self._buffers.items() if k[0] == "accum"}
 
     def workspace(self, m, N, device):
-        """Scratch of one render call, one buffer per (device, stream): calls
-        on one stream reuse it in stream order; renders issued on different
-        streams (concurrent views) never share one."""
+        """(buffer, bytes needed) of one render call: the "render" scratch of
+        this device and stream."""
         need = lib().samnerf_render_workspace_size(ctypes.byref(m), N)
-        key = (device, _stream_key(device))
-        if self._ws is None:
-            self._ws = {}
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-        return ws, need
+        return self._scratch("render", device, need), need
+
+    def _render_workspace(self, base, with_mask, N, device, own):
+        """(buffer, bytes needed, pack_key) of a render: the per-stream
+        workspace with the key of the packed weights it would hold after the
+        render, or with own=True a fresh buffer and None (nothing is reused
+        from it or recorded for it).  Among the per-call fields the size
+        depends on with_mask alone, so without a mask head the size query
+        reads the base itself."""
+        sizing = call_model(base, with_mask=with_mask) if with_mask else base
+        if own:
+            need = lib().samnerf_render_workspace_size(ctypes.byref(sizing), N)
+            return torch.empty(max(need, 1), dtype=torch.uint8, device=device), need, None
+        ws, need = self.workspace(sizing, N, device)
+        return ws, need, pack_key(lib(), ws, base, self._packed_tensors(base))
 
     def fused_mask_ok(self):
         """The network's mask head runs on the fused kernels (mask_kind)."""
@@ -426,85 +603,34 @@ class FusedRenderer:
         rays_d = rays_d.contiguous().float()
         N = rays_o.shape[0]
         dev = rays_o.device
-        m = self.model()
-        m.view_width = int(view_width or 0)
+        # normalise the inputs
+        base = self.model()
         if mask and not self.fused_mask_ok():
             raise NotImplementedError("fused render: this mask head runs on the unfused path")
         # 2: a training render (mask_logits=False): the adaptive heads keep their per-ray input sums
-        m.with_mask = (2 if not mask_logits else 1) if mask else 0
-        pert = None
-        if isinstance(perturb, PhiloxPerturb):
-            pert = perturb
-        elif isinstance(perturb, (tuple, list)) or perturb:    # the GUI passes spp (an int) as perturb
-            pert = tuple(perturb) if isinstance(perturb, (tuple, list)) else \
-                perturbed_positions(N, list(m.num_steps), dev)
-            shapes = [(N, int(m.num_steps[0]) + 1), (N, int(m.num_steps[1]) + 1), (N, int(m.num_steps[2]) + 1)]
-            if len(pert) != 3 or any(tuple(t.shape) != sh for t, sh in zip(pert, shapes)):
-                raise ValueError(f"fused render: perturb arrays must have shapes {shapes}")
-            pert = tuple(t.contiguous().float() for t in pert)
-        set_perturb(m, pert)
-        pack_key = None
-        if own_workspace:
-            need = lib().samnerf_render_workspace_size(ctypes.byref(m), N)
-            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-            m.reuse_packed = 0
-        else:
-            ws, need = self.workspace(m, N, dev)
-            # the packed MLP weights this per-stream workspace holds from its
-            # last render are reused when the weights are the same tensors at
-            # the same version (samnerf_model.reuse_packed: ~25 us per view);
-            # the SAM head's are packed only by renders that run the head
-            head = bool(m.with_sam and feats)
-            pack_key = (ws.data_ptr(), self._pack_signature(m))
-            have = self._packed.get((dev, _stream_key(dev)))
-            m.reuse_packed = int(have is not None and have[0] == pack_key and (have[1] or not head))
+        with_mask = (2 if not mask_logits else 1) if mask else 0
+        pert = resolve_perturb(perturb, N, base.num_steps, dev)
         bg, bg_rows = background_rows(bg_color, N, dev)
-        if out_tile is not None and bg_rows is not None and bg_rows.shape[0] != 1:
-            raise NotImplementedError("fused render: a per-ray background with out_tile (a sharded view "
-                                      "takes a scalar or one colour)")
-        if out_tile is not None:
-            need_c = 261 if (m.with_sam and feats) else 5
-            if (out_tile.dim() != 2 or out_tile.shape[0] != N or out_tile.shape[1] < need_c
-                    or out_tile.dtype != torch.float32 or not out_tile.is_contiguous()
-                    or out_tile.device != dev):
-                raise ValueError(f"fused render: out_tile must be a contiguous fp32 [{N}, >={need_c}] "
-                                 f"tensor on {dev}")
-            if mask:
-                raise NotImplementedError("fused render: out_tile with mask outputs")
-            image, depth, wsum = out_tile[:, 0:3], out_tile[:, 3], out_tile[:, 4]
-            samvit = out_tile[:, 5:261] if need_c == 261 else None
-        else:
-            image = torch.empty(N, 3, device=dev)
-            depth = torch.empty(N, device=dev)
-            wsum = torch.empty(N, device=dev)
-            samvit = torch.empty(N, 256, device=dev) if (m.with_sam and feats) else None
-        cnf = None
-        n_cnf = 0
-        if cam_near_far is not None:
-            cnf = cam_near_far.contiguous().float()
-            n_cnf = cnf.shape[0]
+        cnf = None if cam_near_far is None else cam_near_far.contiguous().float()
+        n_cnf = 0 if cnf is None else cnf.shape[0]
         if rows is not None:
             assert rows.shape == (N, ROW) and rows.is_contiguous()
-        tap = None
-        if taps:
-            steps = [int(v) for v in m.num_steps]
-            stride = 61 if taps is True else int(taps)
-            n_tap = (N + stride - 1) // stride
-            tap = {"ds0": torch.empty(steps[0], N, device=dev), "ds1": torch.empty(steps[1], N, device=dev),
-                   "w0": torch.empty(steps[0], N, device=dev), "w1": torch.empty(steps[1], N, device=dev),
-                   "bins1": torch.empty(steps[1] + 1, N, device=dev),
-                   "bins2": torch.empty(steps[2] + 1, N, device=dev),
-                   "inds1": torch.empty(steps[1] + 1, N, device=dev, dtype=torch.int32),
-                   "inds2": torch.empty(steps[2] + 1, N, device=dev, dtype=torch.int32),
-                   "sigma2": torch.empty(steps[2], N, device=dev), "w2": torch.empty(steps[2], N, device=dev),
-                   "u2": torch.empty(steps[2], 3, N, device=dev)}
-            rows_tap = {"rows2": torch.full((n_tap, steps[2], 16, 8), -1, device=dev, dtype=torch.int32),
-                        "srows": torch.full((n_tap, steps[2], 16, 8), -1, device=dev, dtype=torch.int32)}
-            st = SamnerfTaps(*[t.data_ptr() for t in tap.values()], stride,
-                             rows_tap["rows2"].data_ptr(), rows_tap["srows"].data_ptr())
-            check(lib().samnerf_set_taps(ctypes.byref(st), N), "set_taps")
-        try:
-            set_background(self.net, bg_rows)
+        head = bool(base.with_sam and feats)
+        # the call's model
+        ws, need, key = self._render_workspace(base, with_mask, N, dev, own_workspace)
+        stream_key = (dev, _stream_key(dev))
+        have = self._packed.get(stream_key) if key is not None else None
+        # the packed MLP weights this per-stream workspace holds from its last
+        # render are reused when the weights are the same tensors at the same
+        # version, packed by the same library (samnerf_model.reuse_packed: ~25 us
+        # per view); the SAM head's are packed only by renders that run the head
+        reuse = int(have is not None and have[0] == key and (have[1] or not head))
+        m = call_model(base, view_width=view_width, with_mask=with_mask, perturb=pert, reuse_packed=reuse)
+        # the outputs
+        image, depth, wsum, samvit = _render_outputs(N, dev, head, out_tile, mask, bg_rows)
+        tap = _alloc_taps(m.num_steps, N, taps, dev) if taps else None
+        # the C calls
+        with call_scope(self.net, bg_rows, tap and tap[0], N):
             if out_tile is not None:
                 check(lib().samnerf_render_forward_tile(
                     ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, bg, _ptr(out_tile),
@@ -515,39 +641,20 @@ class FusedRenderer:
                     ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, bg, _ptr(image),
                     _ptr(depth), _ptr(wsum), _ptr(samvit), _ptr(rows), _ptr(ws), need, _stream(rays_o)),
                     "render_forward")
-            self.last_reuse_packed = int(m.reuse_packed)
-            if pack_key is not None:
-                key = (dev, _stream_key(dev))
-                if m.reuse_packed:                 # nothing packed: the head's stays as it was
-                    head = head or self._packed[key][1]
-                self._packed[key] = (pack_key, head)
+            self.last_reuse_packed = reuse
+            if key is not None:
+                # (a reusing render packed nothing: the head's stays as it was)
+                self._packed[stream_key] = (key, bool(head or (reuse and have[1])))
             if mask and mask_logits:
                 logits = torch.empty(N, int(m.mask_out), device=dev)
                 check(lib().samnerf_mask_forward(ctypes.byref(m), N, _ptr(logits), _ptr(ws), need,
                                                  _stream(rays_o)), "mask_forward")
-        finally:
-            if taps:
-                lib().samnerf_set_taps(None, 0)
-            set_perturb(m, None)
-            set_background(None, None)
-            m.reuse_packed = 0
+        # the results
         out = {"image": image, "depth": depth, "weights_sum": wsum}
         if mask and mask_logits:
             out["instance_mask_logits"] = logits
         if tap is not None:
-            # the kernels keep per-sample intermediates in slot order (ray
-            # tiling, samnerf_model.view_width): back to ray order here
-            ray_of = ray_of_slots(N, int(m.view_width)).to(dev)
-            u2 = tap.pop("u2")
-            for k, v in tap.items():
-                r = torch.empty_like(v.t())
-                r[ray_of] = v.t()
-                out[k] = r
-            r = torch.empty_like(u2.permute(2, 0, 1))
-            r[ray_of] = u2.permute(2, 0, 1)
-            out["u2"] = r
-            out.update(rows_tap)
-            out["tap_rays"] = ray_of[torch.arange(0, N, stride, device=dev)].cpu()
+            out.update(_taps_in_ray_order(tap, N, int(m.view_width), dev))
         if samvit is not None:
             out["samvit"] = samvit
         if keep_workspace:
@@ -562,7 +669,7 @@ class FusedRenderer:
         rows = rows.contiguous().float()
         assert rows.dim() == 2 and rows.shape[1] == ROW, rows.shape
         N = rows.shape[0]
-        m = self.model()
+        m = self.call_model()
         need = lib().samnerf_sam_head_workspace_size()
         ws = torch.empty(need, dtype=torch.uint8, device=rows.device)
         out = torch.empty(N, 256, device=rows.device)
@@ -571,23 +678,18 @@ class FusedRenderer:
         return out
 
     def sgrid_backward(self, grad_rows, workspace, grad_embeddings):
-        ws, need, m, view_width = workspace
-        m.view_width = view_width                 # the forward's slot order of the workspace
+        """grad_embeddings += the s_grid gradient of grad_rows [N,164], on the
+        `_workspace` tuple of the forward render (keep_workspace=True,
+        own_workspace=True): its call's struct carries the forward's
+        view_width, the slot order of the workspace."""
+        ws, need, m, _ = workspace
         N = grad_rows.shape[0]
         grad_rows = grad_rows.contiguous()
         assert grad_rows.shape[1] == ROW
         if self.deterministic:
-            # one fixed-point accumulator per (device, stream), like workspace():
-            # calls on one stream reuse it in order (each leaves it zero);
-            # concurrent calls on other streams never share one
+            # the fixed-point accumulator: every call leaves it zero
             size = lib().samnerf_sgrid_accum_size(ctypes.byref(m))
-            dev = grad_rows.device
-            key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-            if self._accum is None:
-                self._accum = {}
-            acc = self._accum.get(key)
-            if acc is None or acc.numel() < size:
-                acc = self._accum[key] = torch.zeros(max(size, 1), dtype=torch.uint8, device=dev)
+            acc = self._scratch("accum", grad_rows.device, size, zero=True)
             check(lib().samnerf_sgrid_backward_det(ctypes.byref(m), _ptr(grad_rows), N,
                                                    _ptr(grad_embeddings), _ptr(acc), acc.numel(), _ptr(ws),
                                                    need, _stream(grad_rows)), "sgrid_backward_det")
@@ -616,9 +718,8 @@ class _FusedSamRows(torch.autograd.Function):
         out = renderer.render(rays_o, rays_d, cam_near_far, bg_color, rows=rows,
                               keep_workspace=True, feats=False, own_workspace=True,
                               view_width=view_width)
-        ctx.ws = out.pop("_workspace")
+        ctx.ws = out.pop("_workspace")           # with the call's struct, for the backward
         ctx.renderer = renderer
-        ctx.keep = list(renderer._keep)
         ctx.emb_shape = s_emb.shape
         ctx.mark_non_differentiable(out["image"], out["depth"], out["weights_sum"])
         return rows, out["image"], out["depth"], out["weights_sum"]
@@ -649,14 +750,14 @@ class _SamHeadTrain(torch.autograd.Function):
     def forward(ctx, rows, renderer, *params):
         rows = rows.contiguous()
         N = rows.shape[0]
-        m = renderer.model()
+        m = renderer.call_model()
         need = lib().samnerf_head_train_workspace_size(N)
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=rows.device)
         samvit = torch.empty(N, 256, device=rows.device)
         check(lib().samnerf_head_train_forward(ctypes.byref(m), _ptr(rows), N, _ptr(samvit), _ptr(ws),
                                                need, _stream(rows)), "head_train_forward")
         ctx.save_for_backward(rows)
-        ctx.ws, ctx.need, ctx.m, ctx.keep = ws, need, m, list(renderer._keep)
+        ctx.ws, ctx.need, ctx.m = ws, need, m
         ctx.shapes = [p.shape for p in params]
         return samvit
 
@@ -712,15 +813,13 @@ class _FusedMaskTrain(torch.autograd.Function):
         dev = rays_o.device
         out = renderer.render(rays_o, rays_d, cnf, bg, keep_workspace=True, feats=False,
                               own_workspace=True, mask=True, mask_logits=False)
-        ws, need, m, vw = out.pop("_workspace")
-        m.with_mask = 2
+        ws, need, m, _ = out.pop("_workspace")     # the render's struct: with_mask 2, its view_width
         tneed = lib().samnerf_mask_train_workspace_size_model(ctypes.byref(m), N)
         tws = torch.empty(max(tneed, 1), dtype=torch.uint8, device=dev)
         logits = torch.empty(N, int(m.mask_out), device=dev)
-        m.with_mask, m.view_width = 2, vw
         check(lib().samnerf_mask_train_forward(ctypes.byref(m), N, _ptr(logits), _ptr(ws), need, _ptr(tws),
                                                tneed, _stream(rays_o)), "mask_train_forward")
-        ctx.state = (m, vw, ws, need, tws, tneed, list(renderer._keep))
+        ctx.state = (m, ws, need, tws, tneed)
         ctx.shapes = tuple(p.shape for p in params)
         ctx.kind = int(m.mask_kind)
         ctx.mark_non_differentiable(out["image"], out["depth"], out["weights_sum"])
@@ -728,14 +827,13 @@ class _FusedMaskTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_logits, g_img, g_depth, g_wsum):
-        m, vw, ws, need, tws, tneed, _ = ctx.state
+        m, ws, need, tws, tneed = ctx.state
         g = g_logits.contiguous().float()          # bound: alive through the C call
         dev = g.device
         adaptive = ctx.kind != 0
         g_emb = None if adaptive else torch.zeros(ctx.shapes[0], device=dev)
         gw = [torch.empty(sh, device=dev) for sh in (ctx.shapes if adaptive else ctx.shapes[1:])]
         arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in gw])
-        m.with_mask, m.view_width = 2, vw
         check(lib().samnerf_mask_train_backward(ctypes.byref(m), g.shape[0], _ptr(g), arr, _ptr(g_emb),
                                                 _ptr(ws), need, _ptr(tws), tneed, _stream(g)),
               "mask_train_backward")
@@ -786,9 +884,7 @@ class _FusedRGBTrain(torch.autograd.Function):
     def forward(ctx, renderer, rays_o, rays_d, cnf, bg, pert, with_prop, *params):
         N = rays_o.shape[0]
         dev = rays_o.device
-        m = renderer.model()
-        m.view_width = 0
-        m.with_mask = 0
+        m = renderer.call_model(perturb=pert)     # the arrays, or the (seed, offset), for the backward too
         need = lib().samnerf_rgb_train_workspace_size(ctypes.byref(m), N)
         ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
         image = torch.empty(N, 3, device=dev)
@@ -798,18 +894,13 @@ class _FusedRGBTrain(torch.autograd.Function):
         losses = torch.zeros(2, device=dev)
         n_cnf = 0 if cnf is None else cnf.shape[0]
         bg, bg_rows = bg                     # background_rows: the scalar, the [n_bg,3] colours or None
-        try:
-            set_perturb(m, pert)
-            set_background(renderer.net, bg_rows)
+        with call_scope(renderer.net, bg_rows):
             check(lib().samnerf_rgb_train_forward(
                 ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, float(bg), int(with_prop),
                 _ptr(image), _ptr(depth), _ptr(wsum), _ptr(weights), _ptr(losses), _ptr(ws), need,
                 _stream(rays_o)),
                 "rgb_train_forward")
-        finally:
-            set_perturb(m, None)
-            set_background(None, None)
-        ctx.state = (renderer, m, rays_o, rays_d, (bg, bg_rows), pert, with_prop, ws, need, list(renderer._keep))
+        ctx.state = (renderer, m, rays_o, rays_d, (bg, bg_rows), with_prop, ws, need)
         ctx.shapes = [p.shape for p in params]
         # outputs the loss does not use arrive as None (no zero tensors to
         # read): only results['weights'] usually is
@@ -818,7 +909,7 @@ class _FusedRGBTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_img, g_depth, g_wsum, g_prop, g_dist, g_weights):
-        renderer, m, rays_o, rays_d, (bg, bg_rows), pert, with_prop, ws, need, _ = ctx.state
+        renderer, m, rays_o, rays_d, (bg, bg_rows), with_prop, ws, need = ctx.state
         dev = rays_o.device
         N = rays_o.shape[0]
         # a loss without proposal_loss leaves the proposal networks' .grad None,
@@ -835,26 +926,13 @@ class _FusedRGBTrain(torch.autograd.Function):
         g_loss = torch.stack([(zero if g_prop is None else g_prop).reshape(()),
                               (zero if g_dist is None else g_dist).reshape(())]).float().contiguous()
         grads = [torch.empty(sh, device=dev) for sh in ctx.shapes]
-        g = SamnerfRgbGrads()
-        g.grid = grads[0].data_ptr()
-        for i in range(3):
-            g.grid_mlp[i] = grads[1 + i].data_ptr()
-            g.view_mlp[i] = grads[4 + i].data_ptr()
-        if with_prop:
-            g.prop[0], g.prop[1] = grads[7].data_ptr(), grads[8].data_ptr()
-            for q in range(2):
-                for i in range(2):
-                    g.prop_mlp[q][i] = grads[9 + 2 * q + i].data_ptr()
-        try:
-            set_perturb(m, pert)             # the forward's arrays, or its (seed, offset)
-            set_background(renderer.net, bg_rows)   # and the forward's mode and colours
+        g = rgb_grads_struct(grads, with_prop)
+        # the forward's struct (its perturb source) under the forward's mode and colours
+        with call_scope(renderer.net, bg_rows):
             check(lib().samnerf_rgb_train_backward(
                 ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, float(bg), int(with_prop), _ptr(g_img),
                 _ptr(g_ws), _ptr(g_dp), _ptr(g_w), _ptr(g_loss),
                 ctypes.byref(g), _ptr(ws), need, _stream(g_img)), "rgb_train_backward")
-        finally:
-            set_perturb(m, None)
-            set_background(None, None)
         if not with_prop:
             grads = grads[:7] + [None] * (len(grads) - 7)
         return (None,) * 7 + tuple(grads)
@@ -875,19 +953,13 @@ def render_rgb_train(renderer, rays_o, rays_d, cam_near_far=None, bg_color=None,
     rays_d = rays_d.contiguous().float()
     N = rays_o.shape[0]
     bg = background_rows(bg_color, N, rays_o.device)
-    m = renderer.model()
-    pert = None
-    if isinstance(perturb, PhiloxPerturb):
-        pert = perturb                   # drawn in the kernels, forward and backward alike
-    elif isinstance(perturb, (tuple, list)) or perturb:
-        pert = tuple(perturb) if isinstance(perturb, (tuple, list)) else \
-            perturbed_positions(N, list(m.num_steps), rays_o.device)
-        pert = tuple(t.contiguous().float() for t in pert)
+    num_steps = list(renderer.model().num_steps)
+    pert = resolve_perturb(perturb, N, num_steps, rays_o.device)
     cnf = None if cam_near_far is None else cam_near_far.contiguous().float()
     with_prop = bool(update_proposal) and getattr(opt, "lambda_proposal", 0) > 0
     image, depth, wsum, prop_loss, dist_loss, weights = _FusedRGBTrain.apply(
         renderer, rays_o, rays_d, cnf, bg, pert, with_prop, *rgb_train_params(net, with_prop))
-    out = {"num_points": N * int(m.num_steps[2]), "weights": weights, "weights_sum": wsum, "depth": depth,
+    out = {"num_points": N * int(num_steps[2]), "weights": weights, "weights_sum": wsum, "depth": depth,
            "image": image}
     if with_prop:
         out["proposal_loss"] = prop_loss

@@ -64,9 +64,9 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     not train)."""
     import ctypes
 
-    from ._lib import SamnerfRgbGrads, SamnerfRgbTrainOpts, check, lib
-    from .fused import (FusedRenderer, PhiloxPerturb, background_rows, perturbed_positions, rgb_train_params,
-                        set_background, set_perturb)
+    from ._lib import SamnerfRgbTrainOpts, check, lib
+    from .fused import (FusedRenderer, background_rows, call_scope, resolve_perturb, rgb_grads_struct,
+                        rgb_train_params)
     from .ops import _ptr, _stream
 
     opt = model.opt
@@ -88,17 +88,7 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     fr = getattr(model, "_fused_train", None)
     if fr is None or fr.net is not model:
         fr = model._fused_train = FusedRenderer(model, head_mode=1)
-    m = fr.model()
-    m.view_width = 0
-    m.with_mask = 0
-    pert = None
-    if isinstance(perturb, PhiloxPerturb):
-        pert = perturb                   # the kernels draw the positions (no arrays)
-    elif isinstance(perturb, (tuple, list)) or perturb:
-        pert = tuple(perturb) if isinstance(perturb, (tuple, list)) else \
-            perturbed_positions(N, list(m.num_steps), dev)
-        pert = tuple(t.contiguous().float() for t in pert)
-    set_perturb(m, pert)
+    m = fr.call_model(perturb=resolve_perturb(perturb, N, fr.model().num_steps, dev))
     o = SamnerfRgbTrainOpts()
     o.lambda_proposal = float(getattr(opt, "lambda_proposal", 0.0))
     o.lambda_distort = float(getattr(opt, "lambda_distort", 0.0))
@@ -118,20 +108,9 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
             raise RuntimeError("rgb_train_step_fused: existing .grad must be float32, on the "
                                "parameter's device and of its shape")
     scratch = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in trained]
-    g = SamnerfRgbGrads()
-    g.grid = scratch[0].data_ptr()
-    for i in range(3):
-        g.grid_mlp[i] = scratch[1 + i].data_ptr()
-        g.view_mlp[i] = scratch[4 + i].data_ptr()
-    if with_prop:
-        g.prop[0], g.prop[1] = scratch[7].data_ptr(), scratch[8].data_ptr()
-        for q in range(2):
-            for i in range(2):
-                g.prop_mlp[q][i] = scratch[9 + 2 * q + i].data_ptr()
+    g = rgb_grads_struct(scratch, with_prop)
     need = lib().samnerf_rgb_train_workspace_size(ctypes.byref(m), N)
-    ws = getattr(fr, "_rt_ws", None)
-    if ws is None or ws.device != dev or ws.numel() < need:
-        ws = fr._rt_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    ws = fr._scratch("rgb_train", dev, need)
     cnf, n_cnf = None, 0
     if cam_near_far is not None:
         cnf = cam_near_far.contiguous().float()
@@ -140,15 +119,11 @@ def rgb_train_step_fused(model, rays_o, rays_d, gt_rgb, global_step, bg_color=No
     depth = torch.empty(N, device=dev)
     wsum = torch.empty(N, device=dev)
     loss = torch.empty(5, device=dev)
-    try:
-        set_background(model, bg_rows)
+    with call_scope(model, bg_rows):
         check(lib().samnerf_rgb_train_step(
             ctypes.byref(m), _ptr(rays_o), _ptr(rays_d), N, _ptr(cnf), n_cnf, _ptr(gt),
             ctypes.byref(o), _ptr(image), _ptr(depth), _ptr(wsum), _ptr(loss), ctypes.byref(g),
             _ptr(ws), need, _stream(rays_o)), "rgb_train_step")
-    finally:
-        set_perturb(m, None)
-        set_background(None, None)
     for p, t in zip(trained, scratch):
         if p.grad is None:
             p.grad = t

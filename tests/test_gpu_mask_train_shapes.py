@@ -225,8 +225,7 @@ def _c_abi_step(fr, ro, rd, g_logits, fill, pattern=None, view_width=0):
     out = fr.render(ro, rd, keep_workspace=True, feats=False, own_workspace=True, mask=True,
                     mask_logits=False, view_width=view_width)
     ws, need, m, vw = out.pop("_workspace")
-    assert vw == view_width
-    m.with_mask, m.view_width = 2, vw
+    assert vw == view_width and (int(m.with_mask), int(m.view_width)) == (2, vw)   # the render's struct
     tneed = lib().samnerf_mask_train_workspace_size_model(ctypes.byref(m), N)
     tws = torch.full((tneed,), fill, dtype=torch.uint8, device=dev)
     logits = torch.full((N, int(m.mask_out)), float("nan"), device=dev)

@@ -123,23 +123,19 @@ def test_seeded_render_rejects_arrays_with_seed(hip_lib, cuda):
     """The C check end to end: perturb_device with arrays set is an error."""
     import ctypes
     from samnerf_amd import _lib
-    from samnerf_amd.fused import FusedRenderer, perturb_fill, set_perturb
+    from samnerf_amd.fused import FusedRenderer, perturb_fill
     from samnerf_amd.ops import _ptr, _stream
     net = _sam_net(cuda)
     ro, rd = _view(8, 8, cuda)
     fr = FusedRenderer(net)
     fr.render(ro, rd)                                   # sizes the workspace
-    m = fr.model()
-    ws, need = fr.workspace(m, 64, ro.device)
     arrays = perturb_fill(SEED, 0, 64, STEPS, cuda)
+    m = fr.call_model(perturb=arrays)                   # this call's own struct
+    m.perturb_device = 1
+    ws, need = fr.workspace(m, 64, ro.device)
     out = [torch.empty(64, 3, device=cuda), torch.empty(64, device=cuda), torch.empty(64, device=cuda)]
-    try:
-        set_perturb(m, arrays)
-        m.perturb_device = 1
-        rc = _lib.lib().samnerf_render_forward(ctypes.byref(m), _ptr(ro), _ptr(rd), 64, None, 0, 1.0, _ptr(out[0]),
-                                               _ptr(out[1]), _ptr(out[2]), None, None, _ptr(ws), need, _stream(ro))
-    finally:
-        set_perturb(m, None)
+    rc = _lib.lib().samnerf_render_forward(ctypes.byref(m), _ptr(ro), _ptr(rd), 64, None, 0, 1.0, _ptr(out[0]),
+                                           _ptr(out[1]), _ptr(out[2]), None, None, _ptr(ws), need, _stream(ro))
     assert rc == -1 and "perturb_device" in _lib.last_error()
 
 

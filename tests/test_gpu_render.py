@@ -716,3 +716,120 @@ def test_packed_weight_reuse(hip_lib, cuda):
     fr2._head_mode = 1                                      # (the model struct is rebuilt)
     g = fr2.render(ro, rd)
     assert fr2.last_reuse_packed == 0 and same(g, FusedRenderer(net, head_mode=1).render(ro, rd))
+
+
+# ------------------------------------------------- per-call model structs --
+
+def _call_model_net(cuda, seed=41):
+    spec = synth.ModelSpec(with_sam=True, grid_log2=14, s_grid_log2=14, prop_log2=12)
+    return make_net(spec, synth.make_params(spec, seed=seed, emb_scale=0.5, ln_jitter=0.1), cuda)
+
+
+def _small_view(W, H, cuda, rot=5):
+    from samnerf_amd import ops
+    pose, intr = synth.gui_camera(W, H, rot=synth.random_rotation(rot))
+    return ops.get_rays(pose, intr, H, W, device=cuda)
+
+
+def test_renders_never_write_the_base_struct(hip_lib, cuda):
+    """FusedRenderer.model() is read-only: after a tiled render, a render with
+    perturb arrays, a seeded one and one with taps its bytes are those from
+    before (every call works on call_model's copy), and it is still the same
+    object.  8 x 8 rays, view_width = 8: the smallest tiled case."""
+    from samnerf_amd.fused import FusedRenderer, PhiloxPerturb, perturb_fill
+    fr = FusedRenderer(_call_model_net(cuda))
+    ro, rd = _small_view(8, 8, cuda)
+    fr.render(ro, rd)
+    base = fr.model()
+    before = bytes(base)
+    arrays = perturb_fill(7, 0, 64, (128, 64, 32), cuda)
+    calls = {"tiled": dict(view_width=8), "arrays": dict(perturb=arrays),
+             "philox": dict(perturb=PhiloxPerturb(7, 3), view_width=8), "taps": dict(taps=True, view_width=8),
+             "kept": dict(keep_workspace=True, own_workspace=True, view_width=8, perturb=arrays)}
+    for name, kw in calls.items():
+        out = fr.render(ro, rd, **kw)
+        assert fr.model() is base and bytes(base) == before, name
+    # the kept call's struct is that call's own
+    m = out["_workspace"][2]
+    assert m is not base and int(m.view_width) == 8 and [m.perturb[i] for i in range(3)] == \
+        [t.data_ptr() for t in arrays]
+    for f in ("view_width", "with_mask", "reuse_packed", "perturb_device", "perturb_seed", "perturb_offset"):
+        assert getattr(base, f) == 0, f
+    assert [base.perturb[i] for i in range(3)] == [None] * 3
+
+
+def test_two_threads_render_through_one_renderer(hip_lib, cuda):
+    """Two threads, each on its own stream, render the same 16 x 8 rays eight
+    times through ONE renderer with different per-call settings (A: 8 x 4 ray
+    tiles and its seed, B: row-major waves and another seed): every output
+    equals, bit for bit, the same call made serially on a fresh renderer.
+    Same N and no perturb arrays in both threads: a leftover race on the
+    struct could only give wrong values, never a wrong address."""
+    import threading
+    from samnerf_amd.fused import FusedRenderer, PhiloxPerturb
+    net = _call_model_net(cuda)
+    ro, rd = _small_view(16, 8, cuda)
+    keys = ("image", "depth", "weights_sum", "samvit")
+    plans = {"A": (8, 0xA11CE), "B": (0, 0xB0B0B0B0B0B)}
+    want = {t: [FusedRenderer(net).render(ro, rd, view_width=vw, perturb=PhiloxPerturb(seed, i))
+                for i in range(8)] for t, (vw, seed) in plans.items()}
+    assert not torch.equal(want["A"][0]["image"], want["B"][0]["image"])      # the seeds act
+    assert not torch.equal(want["A"][0]["image"], want["A"][1]["image"])      # and the offsets
+    fr = FusedRenderer(net)
+    fr.render(ro, rd)                                                         # warm: the base struct is built
+    torch.cuda.synchronize()
+    got, errors = {}, []
+    go = threading.Barrier(2)
+
+    def work(name):
+        try:
+            vw, seed = plans[name]
+            with torch.cuda.stream(torch.cuda.Stream(device=cuda)):
+                go.wait(timeout=30)
+                got[name] = [fr.render(ro, rd, view_width=vw, perturb=PhiloxPerturb(seed, i)) for i in range(8)]
+        except BaseException as e:          # reported by the main thread
+            go.abort()
+            errors.append((name, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(n,)) for n in plans]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    torch.cuda.synchronize()
+    assert not errors, errors
+    for name in plans:
+        for i in range(8):
+            for k in keys:
+                assert torch.equal(got[name][i][k], want[name][i][k]), (name, i, k)
+
+
+def test_packed_weight_reuse_across_libraries(hip_lib, cuda):
+    """The packed-weight record names the library that packed: on one renderer
+    a product render, a render through the diagnostic library's h16q head form
+    (another packed layout) and a product render again -- the last one repacks
+    and equals a fresh renderer's bit for bit; the one after it reuses."""
+    from samnerf_amd import _lib
+    from samnerf_amd.fused import FusedRenderer
+    net = _call_model_net(cuda, seed=43)
+    ro, rd = _small_view(8, 8, cuda)
+    keys = ("image", "depth", "weights_sum", "samvit")
+
+    def same(a, b):
+        return all(torch.equal(a[k], b[k]) for k in keys)
+
+    fresh = FusedRenderer(net).render(ro, rd)
+    fr = FusedRenderer(net)
+    a = fr.render(ro, rd)
+    assert fr.last_reuse_packed == 0 and same(a, fresh)
+    try:
+        with _lib.diag_library():
+            os.environ["SAMNERF_HEAD_V"] = "0"
+            fr.render(ro, rd)
+            assert fr.last_reuse_packed == 0           # nor does the product's packing vouch for the diagnostic render
+    finally:
+        os.environ.pop("SAMNERF_HEAD_V", None)
+    b = fr.render(ro, rd)
+    assert fr.last_reuse_packed == 0 and same(b, fresh)
+    c = fr.render(ro, rd)
+    assert fr.last_reuse_packed == 1 and same(c, fresh)

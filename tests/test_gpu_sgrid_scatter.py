@@ -318,8 +318,7 @@ def test_c_abi_refuses_before_any_launch(hip_lib, cuda):
     from samnerf_amd.fused import FusedRenderer
     OK, EINVAL, EWORKSPACE = 0, -1, -3
     c = _get(cuda, ("first37", 37, 0, 14))
-    ws, need, m, vw = c.ws
-    m.view_width = vw
+    ws, need, m, _ = c.ws                                # the render's struct, its view_width
     size = lib().samnerf_sgrid_accum_size(ctypes.byref(m))
     acc = torch.zeros(size, dtype=torch.uint8, device=cuda)
     ge = torch.zeros_like(c.emb)

@@ -213,8 +213,7 @@ def test_sgrid_backward_deterministic_nonfinite_and_size(hip_lib, cuda):
     fr.sgrid_backward(g, ws, again)
     assert torch.equal(again, clean)                         # the accumulator was left clean
     # C ABI: a too-small accumulator is refused before any launch
-    wsb, need, m, vw = ws
-    m.view_width = vw
+    wsb, need, m, _ = ws                                    # the render's struct, its view_width
     size = lib().samnerf_sgrid_accum_size(ctypes.byref(m))
     small = torch.zeros(size - 8, dtype=torch.uint8, device=cuda)
     rc = lib().samnerf_sgrid_backward_det(ctypes.byref(m), ctypes.c_void_p(g.data_ptr()), N,
@@ -611,3 +610,71 @@ def test_distillation_step_with_ray_tiles(hip_lib, cuda):
     assert torch.equal(res[0][0], res[1][0])
     for a, b in zip(res[0][1], res[1][1]):
         assert ((a - b).norm() / b.norm().clamp_min(1e-12)).item() < 1e-5
+
+
+# ------------------------------------------------- per-call model structs --
+
+def _small_view(W, H, cuda, rot=5):
+    from samnerf_amd import ops
+    pose, intr = synth.gui_camera(W, H, rot=synth.random_rotation(rot))
+    return ops.get_rays(pose, intr, H, W, device=cuda)
+
+
+def test_training_renders_never_write_the_base_struct(hip_lib, cuda):
+    """FusedRenderer.model() keeps its bytes (and stays the same object) over a
+    distillation render with ray tiles, an RGB training render with
+    perturb=True and a mask training render, forward and backward each -- the
+    RGB and the mask step on a model of their kind and its own renderer (the
+    C entry points refuse other models).  8 x 8 rays."""
+    from samnerf_amd.fused import FusedRenderer, render_mask_train, render_rgb_train, render_sam_train
+    ro, rd = _small_view(8, 8, cuda)
+    rgb_spec = synth.ModelSpec(with_sam=False, grid_log2=12, s_grid_log2=10, prop_log2=10)
+    mask_spec = synth.ModelSpec(with_sam=False, with_mask=True, mask_type="default", n_inst=3, redundant_instance=2,
+                                grid_log2=14, prop_log2=12, m_grid_log2=14)
+    steps = [
+        (_frozen_net(cuda).train(), {}, lambda fr: render_sam_train(fr, ro, rd, view_width=8)["samvit"]),
+        (make_net(rgb_spec, synth.make_params(rgb_spec, seed=12, emb_scale=0.5), cuda).train(), dict(head_mode=1),
+         lambda fr: render_rgb_train(fr, ro, rd, perturb=True)["image"]),
+        (make_net(mask_spec, synth.make_params(mask_spec, seed=12, emb_scale=0.5), cuda).train(), {},
+         lambda fr: render_mask_train(fr, ro, rd)["instance_mask_logits"]),
+    ]
+    for net, kw, step in steps:
+        fr = FusedRenderer(net, **kw)
+        fr.render(ro, rd)
+        base = fr.model()
+        before = bytes(base)
+        with torch.enable_grad():
+            out = step(fr)
+        assert fr.model() is base and bytes(base) == before, "forward"
+        out.sum().backward()
+        assert any(p.grad is not None and bool(p.grad.any()) for p in net.parameters())
+        assert fr.model() is base and bytes(base) == before, "backward"
+
+
+@pytest.mark.parametrize("W", [8, 16])
+def test_saved_distillation_call_survives_later_renders(hip_lib, cuda, W):
+    """The backward of render_sam_train(view_width=W) uses its forward's own
+    struct: a plain render of another ray count and a seeded render on the
+    same renderer between forward and backward change nothing -- the gradients
+    of s_grid.embeddings and the 12 head tensors are bit-equal to the step
+    with nothing in between (deterministic scatter, which repeats bit for
+    bit).  W x 8 rays: 64 (the smallest tiled view) and 128 (two waves)."""
+    from samnerf_amd.fused import FusedRenderer, PhiloxPerturb, render_sam_train
+    net = _frozen_net(cuda).train()
+    ro, rd = _small_view(W, 8, cuda)
+    ro2, rd2 = _small_view(12, 5, cuda, rot=9)                  # 60 rays, untiled
+    G = torch.randn(W * 8, 256, device=cuda, generator=torch.Generator(device=cuda).manual_seed(8))
+    fr = FusedRenderer(net, deterministic=True)
+    grads = []
+    for between in (False, True):
+        net.zero_grad(set_to_none=True)
+        out = render_sam_train(fr, ro, rd, view_width=W)["samvit"]
+        if between:
+            fr.render(ro2, rd2, view_width=0)
+            fr.render(ro, rd, perturb=PhiloxPerturb(5, 1))
+        (out * G).sum().backward()
+        grads.append({k: p.grad.clone() for k, p in net.named_parameters() if p.grad is not None})
+    assert len(grads[0]) == 13 and set(grads[0]) == set(grads[1])
+    assert bool(grads[0]["s_grid.embeddings"].any())
+    for k in grads[0]:
+        assert torch.equal(grads[0][k], grads[1][k]), k

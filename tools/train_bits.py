@@ -70,7 +70,7 @@ def sam_head_bits(dev, out, sizes):
         for p in params:
             p.grad = None
     sizes["head_train"] = [int(lib().samnerf_head_train_workspace_size(n)) for n in SIZES_N]
-    m = fr.model()
+    m = fr.call_model()
     sizes["render_sam"] = [int(lib().samnerf_render_workspace_size(ctypes.byref(m), n)) for n in SIZES_N]
 
 
@@ -86,8 +86,7 @@ def mask_bits(dev, out, sizes):
             ro, rd = rays(dev, n)
             logits = render_mask_train(FusedRenderer(net), ro, rd)["instance_mask_logits"]
             out[f"mask_logits_h{head_mode}_N{n}"] = sha(logits)
-    m = FusedRenderer(net).model()
-    m.with_mask = 2
+    m = FusedRenderer(net).call_model(with_mask=2)
     sizes["mask_train"] = [int(lib().samnerf_mask_train_workspace_size(n)) for n in SIZES_N]
     sizes["render_mask"] = [int(lib().samnerf_render_workspace_size(ctypes.byref(m), n)) for n in SIZES_N]
 
@@ -106,16 +105,14 @@ def adaptive_bits(dev, out, sizes):
     logits.backward(torch.randn(37, 5, generator=torch.Generator().manual_seed(9)).to(dev))
     out["adaptive_density_N37"] = dict({"logits": sha(logits)},
                                        **{f"w{i}": sha(layer.weight.grad) for i, layer in enumerate(net.mask_mlp)})
-    m = FusedRenderer(net).model()
-    m.with_mask = 2
+    m = FusedRenderer(net).call_model(with_mask=2)
     sizes["render_adaptive_train"] = [int(lib().samnerf_render_workspace_size(ctypes.byref(m), n)) for n in SIZES_N]
 
 
 def rgb_sizes(dev, sizes):
     from samnerf_amd._lib import lib
     from samnerf_amd.fused import FusedRenderer
-    m = FusedRenderer(make_net(dev, 12, with_sam=False)).model()
-    m.view_width = 0
+    m = FusedRenderer(make_net(dev, 12, with_sam=False)).call_model()
     sizes["rgb_train"] = [int(lib().samnerf_rgb_train_workspace_size(ctypes.byref(m), n)) for n in SIZES_N]
     sizes["render_rgb"] = [int(lib().samnerf_render_workspace_size(ctypes.byref(m), n)) for n in SIZES_N]
 
