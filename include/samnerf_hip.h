@@ -1297,6 +1297,74 @@ int samnerf_sam_decoder_launches(void);
 int samnerf_sam_masks(const float* low_res, uint32_t M, uint32_t g, uint32_t in_h, uint32_t in_w, uint32_t H,
                       uint32_t W, float* logits, uint8_t* mask, samnerf_stream_t stream);
 
+/* ------------------------------------------- SAM decoder: prompt batches --
+ * B prompt sets of P points each over one image embedding: what SAM's
+ * automatic mask generator runs per chunk of its point grid.  The kernels of
+ * the single call with a batch axis: image-side linears on B N rows (image_pe
+ * and the weights read by every set), token-side kernels on B T rows, the
+ * attentions, the norm and the upscale with the set in the grid.  What does
+ * not depend on the prompt runs once a call: the source tokens, layer 0's
+ * token->image k / v projections and layer 0's image->token q projection (the
+ * image tokens first change at the end of layer 0).  Every accumulation order
+ * is the single call's, so set b of a batch has the bits of a single call on
+ * points[b]; for whole-number coordinates those of the int32 entry.  The
+ * launch count depends on no argument (samnerf_sam_decoder_launches).
+ *
+ * points [B][P][2] fp32 (x, y) in the S frame and labels [B][P] int32, both
+ * ON THE DEVICE; a label is read as label != 0.  features, h, w as above.
+ * low_res [B][4][4g][4g], iou [B][4].  SAMNERF_EINVAL before any launch: g as
+ * above, B outside [1, 256], P outside [1, 58], a null pointer, pack / iou /
+ * workspace not 16-byte aligned, a short pack, h / w as above.
+ * SAMNERF_EWORKSPACE: a workspace smaller than
+ * samnerf_sam_decoder_batch_workspace_size(g, B) (0 for a bad g or B). */
+size_t samnerf_sam_decoder_batch_workspace_size(uint32_t g, uint32_t B);
+
+int samnerf_sam_decoder_batch(const void* pack, size_t pack_bytes, uint32_t g, const float* features, uint32_t h,
+                              uint32_t w, const float* points, const int32_t* labels, uint32_t B, uint32_t P,
+                              float* low_res, float* iou, void* workspace, size_t workspace_bytes,
+                              samnerf_stream_t stream);
+
+/* The gather form of samnerf_sam_masks: output slot s is mask index[s] (index
+ * NULL: s) of the table low_res [n][4g][4g], n in [1, 12288].  `count` slots
+ * are launched; with count_dev (a device int32) only slots below *count_dev
+ * are written and the others keep what they held, as does a slot whose index
+ * lies outside the table.  logits / mask [count][H][W], the expression of
+ * samnerf_sam_masks bit for bit; mask = logit > mask_threshold (SAM's is 0).  count = 0 succeeds with no launch. */
+int samnerf_sam_masks_select(const float* low_res, uint32_t n, const int32_t* index, uint32_t count,
+                             const int32_t* count_dev, uint32_t g, uint32_t in_h, uint32_t in_w, uint32_t H,
+                             uint32_t W, float mask_threshold, float* logits, uint8_t* mask,
+                             samnerf_stream_t stream);
+
+/* One record of SAMNERF_SAM_REC_WORDS 32-bit words per mask candidate:
+ *   0 inter  = #(logit > mask_threshold + stability_score_offset)
+ *   1 union  = #(logit > mask_threshold - stability_score_offset)
+ *   2 area   = #(logit > mask_threshold)
+ *   3..6 x0, y0, x1, y1 of (logit > mask_threshold): min / max column and row,
+ *        the max inclusive (batched_mask_to_box); 0, 0, 0, 0 for an empty mask
+ *   7 stability = (float)inter / (float)union, its fp32 bits
+ *   8 pass   = (iou > pred_iou_thresh) && (stability >= stability_score_thresh)
+ *   9 iou, its fp32 bits
+ * over the (H, W) view, the logit being samnerf_sam_masks' expression kept in
+ * registers.  A candidate failing the IoU test is not walked: its record is
+ * all zero.  NaN compares false.  Integer sums and min / max, no atomics.
+ * n in [0, 12288]; n = 0 succeeds with no launch. */
+#define SAMNERF_SAM_REC_WORDS 10
+
+int samnerf_sam_mask_stats(const float* low_res, const float* iou, uint32_t n, uint32_t g, uint32_t in_h,
+                           uint32_t in_w, uint32_t H, uint32_t W, float pred_iou_thresh, float mask_threshold,
+                           float stability_score_offset, float stability_score_thresh, int32_t* records,
+                           samnerf_stream_t stream);
+
+/* Greedy box NMS over the passing records, on the device: descending iou,
+ * ties to the lower index; a later box is suppressed when
+ * inter / (a_i + a_j - inter) > box_nms_thresh in fp32, inter =
+ * max(0, min(x1) - max(x0)) * max(0, min(y1) - max(y0)), a = (x1 - x0)(y1 - y0)
+ * on the boxes as floats (torchvision's nms); 0 / 0 suppresses nothing.
+ * keep [n] int32: the kept indices in that order, then -1; *count their
+ * number.  n in [0, 12288]; n = 0 succeeds with no launch and writes nothing. */
+int samnerf_sam_nms(const int32_t* records, uint32_t n, float box_nms_thresh, int32_t* keep, int32_t* count,
+                    samnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,15 @@
 //                 [32][4g][4g] tensor is never written
 // and samnerf_sam_masks is one more: both resizes of the postprocess as 16 taps
 // per output pixel, the S x S intermediate never written.
+//
+// samnerf_sam_decoder_batch is the same 44 launches for B prompt sets: the
+// kernels' batched forms (template parameter BC / BATCH; the single call keeps
+// its own instantiations) run the image side on B N rows and the token side on
+// B T rows, what does not depend on the prompt once a call, every sum in the
+// single call's order, so a set's bits are those of its single call.  The mask
+// generator's steps follow: k_sd_masks_select (the postprocess as a gather),
+// k_sd_mask_stats (a candidate's areas, box and filters, the logits in
+// registers), k_sd_nms_rank / k_sd_nms_greedy (box NMS on the device).
 #include <atomic>
 #include <cmath>
 #include <vector>
@@ -278,6 +287,32 @@ __global__ void __launch_bounds__(kT) k_sd_tokens(TokArgs a) {
     a.q[(size_t)row * kC + c] = v;
 }
 
+// The batched call's tokens: rows [B][T], the points and labels read from the
+// device.  A whole-number coordinate gives k_sd_tokens' bits ((float)x is it);
+// a label is read as label != 0.
+__global__ void __launch_bounds__(kT) k_sd_tokens_batch(const float* __restrict__ pack, size_t G, size_t pt0,
+                                                        size_t pt1, size_t nap, size_t iou, size_t mtok,
+                                                        const float* __restrict__ points,
+                                                        const int32_t* __restrict__ labels, float* __restrict__ tok,
+                                                        float* __restrict__ q, uint32_t P, uint32_t S) {
+    const uint32_t T = P + 6u, b = blockIdx.x / T, row = blockIdx.x - b * T, c = threadIdx.x;
+    float v;
+    if (row == 0u) {
+        v = pack[iou + c];
+    } else if (row < 5u) {
+        v = pack[mtok + (size_t)(row - 1u) * kC + c];
+    } else if (row < 5u + P) {
+        const size_t p = (size_t)b * P + (row - 5u);
+        const float Sf = (float)S;
+        v = pos_code(pack + G, (points[2u * p] + 0.5f) / Sf, (points[2u * p + 1u] + 0.5f) / Sf, c) +
+            pack[(labels[p] != 0 ? pt1 : pt0) + c];
+    } else {
+        v = pack[nap + c];
+    }
+    tok[(size_t)blockIdx.x * kC + c] = v;
+    q[(size_t)blockIdx.x * kC + c] = v;
+}
+
 // ------------------------------------------------------------------ GEMM --
 
 struct LinJob {
@@ -288,6 +323,7 @@ struct LinJob {
     const float* R;     // [M][O] added after the activation, or null
     float* Y;           // [M][O]
     uint32_t M, K, O, lda, relu;
+    uint32_t a2_mod, r_mod;   // the batched call's broadcasts: row r reads A2 / R at r % mod (0: at r)
 };
 struct LinJobs {
     LinJob j[kMaxJobs];
@@ -295,8 +331,10 @@ struct LinJobs {
 
 // TM rows x 64 columns a workgroup, K in steps of 32 through LDS with the next
 // step's loads in flight over the FMAs; a thread holds TM / 16 rows x 4 columns.
-// Every output is one chain of FMAs over k = 0 .. K - 1.
-template <int TM>
+// Every output is one chain of FMAs over k = 0 .. K - 1.  BC: the batched call's
+// form, in which A2 and R may be one set's rows read by every set (a2_mod,
+// r_mod); the sums are the same chains.
+template <int TM, bool BC = false>
 __global__ void __launch_bounds__(kT) k_sd_lin(LinJobs J) {
     constexpr int KC = 32, TN = 64, RM = TM / 16;
     constexpr int A4 = TM * KC / 4, NA = (A4 + 255) / 256, NW = KC * TN / 4 / 256;
@@ -318,7 +356,9 @@ __global__ void __launch_bounds__(kT) k_sd_lin(LinJobs J) {
                 if (r < j.M) {
                     v = *reinterpret_cast<const float4*>(j.A + (size_t)r * j.lda + k);
                     if (j.A2) {
-                        const float4 u = *reinterpret_cast<const float4*>(j.A2 + (size_t)r * j.lda + k);
+                        uint32_t r2 = r;
+                        if constexpr (BC) r2 = j.a2_mod ? r % j.a2_mod : r;
+                        const float4 u = *reinterpret_cast<const float4*>(j.A2 + (size_t)r2 * j.lda + k);
                         v = make_float4(v.x + u.x, v.y + u.y, v.z + u.z, v.w + u.w);
                     }
                 }
@@ -386,7 +426,9 @@ __global__ void __launch_bounds__(kT) k_sd_lin(LinJobs J) {
         float4 v = make_float4(acc[r][0] + b.x, acc[r][1] + b.y, acc[r][2] + b.z, acc[r][3] + b.w);
         if (j.relu) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
         if (j.R) {
-            const float4 u = *reinterpret_cast<const float4*>(j.R + (size_t)row * j.O + col);
+            uint32_t rr = row;
+            if constexpr (BC) rr = j.r_mod ? row % j.r_mod : row;
+            const float4 u = *reinterpret_cast<const float4*>(j.R + (size_t)rr * j.O + col);
             v = make_float4(v.x + u.x, v.y + u.y, v.z + u.z, v.w + u.w);
         }
         *reinterpret_cast<float4*>(j.Y + (size_t)row * j.O + col) = v;
@@ -407,13 +449,29 @@ __device__ __forceinline__ float part_weight(float m, float mn) { return m == -I
 // to part [slice][T][8][DH + 2] and k_sd_attn_merge combines them in slice
 // order -- a few queries over 4,096 keys would otherwise run on T / QB x 8
 // workgroups, each reading every key's head slice.
-template <int DH, int QB, int U>
+//
+// BATCH: blockIdx.x also counts the prompt sets, div_up(T, QB) workgroups
+// each; set b's queries are rows b T .. of Q, out and (per slice) part, its
+// keys start at b * kv_stride floats of K and V (0: every set reads the same).
+template <int DH, int QB, int U, bool BATCH = false>
 __global__ void __launch_bounds__(kT) k_sd_attn_tok(const float* __restrict__ Q, const float* __restrict__ K,
                                                     const float* __restrict__ V, float* __restrict__ out,
-                                                    float* __restrict__ part, uint32_t T, uint32_t Nk) {
+                                                    float* __restrict__ part, uint32_t T, uint32_t Nk,
+                                                    uint32_t sets = 1, size_t kv_stride = 0) {
     constexpr uint32_t inner = kHeads * DH;
     __shared__ float sh[4][QB][DH + 2];
-    const uint32_t h = blockIdx.y, q0 = blockIdx.x * QB, t = threadIdx.x;
+    uint32_t bx = blockIdx.x, Ttot = T;
+    if constexpr (BATCH) {
+        const uint32_t per_set = (T + QB - 1) / QB, b = bx / per_set;
+        bx -= b * per_set;
+        Q += (size_t)b * T * inner;
+        K += (size_t)b * kv_stride;
+        V += (size_t)b * kv_stride;
+        out += (size_t)b * T * inner;
+        part += (size_t)b * T * kHeads * (DH + 2);
+        Ttot = sets * T;
+    }
+    const uint32_t h = blockIdx.y, q0 = bx * QB, t = threadIdx.x;
     float q[QB][DH], acc[QB][DH], m[QB], l[QB];
 #pragma unroll
     for (int qi = 0; qi < QB; ++qi) {
@@ -489,7 +547,7 @@ __global__ void __launch_bounds__(kT) k_sd_attn_tok(const float* __restrict__ Q,
         if (gridDim.z == 1u) {
             out[(size_t)(q0 + qi) * inner + h * DH + d] = a / ll;
         } else {
-            float* p = part + (((size_t)blockIdx.z * T + q0 + qi) * kHeads + h) * (DH + 2);
+            float* p = part + (((size_t)blockIdx.z * Ttot + q0 + qi) * kHeads + h) * (DH + 2);
             p[d] = a;
             if (d == 0u) {
                 p[DH] = mm;
@@ -521,11 +579,21 @@ __global__ void __launch_bounds__(128) k_sd_attn_merge(const float* __restrict__
 
 // Image -> token: a thread is one image token and one head (16 wide) over the
 // T token keys in index order.
+// BATCH: blockIdx.z is the prompt set; its keys are rows b T .., its outputs
+// rows b N .., its queries start at b * q_stride floats (0: the same for all).
+template <bool BATCH = false>
 __global__ void __launch_bounds__(kT) k_sd_attn_img(const float* __restrict__ Q, const float* __restrict__ K,
                                                     const float* __restrict__ V, float* __restrict__ out, uint32_t N,
-                                                    uint32_t T) {
+                                                    uint32_t T, size_t q_stride = 0) {
     constexpr uint32_t DH = 16, inner = 128;
     __shared__ float4 Ks[kMaxTok * 4], Vs[kMaxTok * 4];
+    if constexpr (BATCH) {
+        const uint32_t b = blockIdx.z;
+        Q += (size_t)b * q_stride;
+        K += (size_t)b * T * inner;
+        V += (size_t)b * T * inner;
+        out += (size_t)b * N * inner;
+    }
     const uint32_t h = blockIdx.y, t = threadIdx.x;
     for (uint32_t i = t; i < T * 4u; i += kT) {
         const size_t at = (size_t)(i >> 2) * inner + h * DH + (i & 3u) * 4u;
@@ -597,6 +665,10 @@ __device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(
 // ij = 2 i + j of its 2 x 2 block.  A thread is (token, ij, sub-pixel): the
 // pixel's LayerNorm2d (eps 1e-6) and GELU, the 32 channels of its sub-pixel
 // of the second transposed convolution, GELU, the four hypernetwork products.
+// BATCH: blockIdx.y is the prompt set: u1 [B][N][4][64], hyp [4][B][32] (the
+// batched linears write a mask's products of every set together), low
+// [B][4][4g][4g].
+template <bool BATCH = false>
 __global__ void __launch_bounds__(kT) k_sd_up(const float* __restrict__ u1, const float* __restrict__ lnw,
                                               const float* __restrict__ lnb, const float* __restrict__ w2,
                                               const float* __restrict__ b2, const float* __restrict__ hyp,
@@ -609,7 +681,14 @@ __global__ void __launch_bounds__(kT) k_sd_up(const float* __restrict__ u1, cons
         const uint32_t c = i / 32u, rem = i % 32u, sub = rem / 8u, o4 = rem % 8u;
         W4[(c * kW2Row + sub * 36u) / 4u + o4] = reinterpret_cast<const float4*>(w2)[i];
     }
-    if (t < 32u) H4[t] = reinterpret_cast<const float4*>(hyp)[t];
+    if constexpr (BATCH) {
+        const uint32_t b = blockIdx.y, B = gridDim.y;
+        u1 += (size_t)b * g * g * kC;
+        low += (size_t)b * 64u * g * g;
+        if (t < 32u) H4[t] = reinterpret_cast<const float4*>(hyp)[((t >> 3) * B + b) * 8u + (t & 7u)];
+    } else {
+        if (t < 32u) H4[t] = reinterpret_cast<const float4*>(hyp)[t];
+    }
     if (t < 8u) B4[t] = reinterpret_cast<const float4*>(b2)[t];      // the bias of one sub-pixel: b2 is tiled
     // g * g is a multiple of 64, so every workgroup has its 16 tokens
     const uint32_t pair = t >> 2, sub = t & 3u;
@@ -687,37 +766,232 @@ struct MaskArgs {
 
 // One output pixel: the 2 x 2 taps of the resize (ih, iw) -> (H, W), each a
 // 2 x 2 tap of the resize L -> S.  The crop to (ih, iw) only bounds the taps.
-__global__ void __launch_bounds__(kT) k_sd_masks(MaskArgs a) {
-    const uint32_t i = blockIdx.x * kT + threadIdx.x;
-    if (i >= a.H * a.W) return;
-    const uint32_t Y = i / a.W, X = i - Y * a.W;
+// p is the mask's [L][L] image.  The one expression of k_sd_masks,
+// k_sd_masks_select and k_sd_mask_stats (the build contracts nothing, so the
+// three give the same bits).
+__device__ __forceinline__ float mask_logit(const float* __restrict__ p, uint32_t L, uint32_t S, uint32_t ih,
+                                            uint32_t iw, uint32_t H, uint32_t W, uint32_t Y, uint32_t X) {
     uint32_t sy[2], sx[2];
     float wy[2], wx[2];
-    bilinear_tap(a.ih, a.H, Y, sy[0], sy[1], wy[1]);
-    bilinear_tap(a.iw, a.W, X, sx[0], sx[1], wx[1]);
+    bilinear_tap(ih, H, Y, sy[0], sy[1], wy[1]);
+    bilinear_tap(iw, W, X, sx[0], sx[1], wx[1]);
     wy[0] = 1.0f - wy[1];
     wx[0] = 1.0f - wx[1];
     uint32_t y0[2], y1[2], x0[2], x1[2];
     float ly[2], lx[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        bilinear_tap(a.L, a.S, sy[k], y0[k], y1[k], ly[k]);
-        bilinear_tap(a.L, a.S, sx[k], x0[k], x1[k], lx[k]);
+        bilinear_tap(L, S, sy[k], y0[k], y1[k], ly[k]);
+        bilinear_tap(L, S, sx[k], x0[k], x1[k], lx[k]);
     }
-    const float* p = a.low + (size_t)blockIdx.y * a.L * a.L;
     float v[2][2];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const float mx = 1.0f - lx[c], my = 1.0f - ly[r];
-            v[r][c] = my * (mx * p[y0[r] * a.L + x0[c]] + lx[c] * p[y0[r] * a.L + x1[c]]) +
-                      ly[r] * (mx * p[y1[r] * a.L + x0[c]] + lx[c] * p[y1[r] * a.L + x1[c]]);
+            v[r][c] = my * (mx * p[y0[r] * L + x0[c]] + lx[c] * p[y0[r] * L + x1[c]]) +
+                      ly[r] * (mx * p[y1[r] * L + x0[c]] + lx[c] * p[y1[r] * L + x1[c]]);
         }
-    const float out = wy[0] * (wx[0] * v[0][0] + wx[1] * v[0][1]) + wy[1] * (wx[0] * v[1][0] + wx[1] * v[1][1]);
+    return wy[0] * (wx[0] * v[0][0] + wx[1] * v[0][1]) + wy[1] * (wx[0] * v[1][0] + wx[1] * v[1][1]);
+}
+
+__global__ void __launch_bounds__(kT) k_sd_masks(MaskArgs a) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x;
+    if (i >= a.H * a.W) return;
+    const uint32_t Y = i / a.W, X = i - Y * a.W;
+    const float out = mask_logit(a.low + (size_t)blockIdx.y * a.L * a.L, a.L, a.S, a.ih, a.iw, a.H, a.W, Y, X);
     const size_t at = (size_t)blockIdx.y * a.H * a.W + i;
     if (a.logits) a.logits[at] = out;
     if (a.mask) a.mask[at] = out > 0.0f ? 1 : 0;
+}
+
+// The gather form: output slot blockIdx.y is mask index[slot] (null: slot) of a
+// table of n; slots at and past *count (null: all `cap` slots are live) are
+// left as they are, and so is a slot whose index is outside the table.
+struct SelectArgs {
+    MaskArgs m;
+    const int32_t* index;
+    const int32_t* count;
+    uint32_t n;
+    float thr;            // mask = logit > thr
+};
+
+__global__ void __launch_bounds__(kT) k_sd_masks_select(SelectArgs a) {
+    const uint32_t i = blockIdx.x * kT + threadIdx.x, slot = blockIdx.y;
+    if (i >= a.m.H * a.m.W) return;
+    if (a.count && (int32_t)slot >= *a.count) return;
+    const uint32_t src = a.index ? (uint32_t)a.index[slot] : slot;
+    if (src >= a.n) return;
+    const uint32_t Y = i / a.m.W, X = i - Y * a.m.W;
+    const float out = mask_logit(a.m.low + (size_t)src * a.m.L * a.m.L, a.m.L, a.m.S, a.m.ih, a.m.iw, a.m.H, a.m.W, Y, X);
+    const size_t at = (size_t)slot * a.m.H * a.m.W + i;
+    if (a.m.logits) a.m.logits[at] = out;
+    if (a.m.mask) a.m.mask[at] = out > a.thr ? 1 : 0;
+}
+
+// ------------------------------------------------------ generator: stats --
+
+// A candidate's record, SAMNERF_SAM_REC_WORDS 32-bit words (samnerf_hip.h).
+enum { kRecInter, kRecUnion, kRecArea, kRecX0, kRecY0, kRecX1, kRecY1, kRecStab, kRecPass, kRecIou, kRecWords };
+static_assert(kRecWords == SAMNERF_SAM_REC_WORDS, "record layout");
+
+struct StatsArgs {
+    MaskArgs m;
+    const float* iou;
+    int32_t* rec;
+    float iou_thresh, thr, off, stab_thresh;
+};
+
+// A workgroup a candidate.  One failing the IoU test costs a zeroed record;
+// the others walk the view's pixels, thread t pixels t, t + 256, ..., with
+// the logit of k_sd_masks in registers only, and reduce three counts and a
+// box: integers, so the order of the reduction does not show.
+__global__ void __launch_bounds__(kT) k_sd_mask_stats(StatsArgs a) {
+    __shared__ int32_t sh[4][7];
+    const uint32_t c = blockIdx.x, t = threadIdx.x;
+    int32_t* rec = a.rec + (size_t)c * kRecWords;
+    const float iou = a.iou[c];
+    if (!(iou > a.iou_thresh)) {                          // a NaN score fails
+        if (t < (uint32_t)kRecWords) rec[t] = 0;
+        return;
+    }
+    const float* p = a.m.low + (size_t)c * a.m.L * a.m.L;
+    const float hi = a.thr + a.off, lo = a.thr - a.off;
+    const uint32_t n = a.m.H * a.m.W;
+    int32_t inter = 0, uni = 0, area = 0, x0 = INT32_MAX, y0 = INT32_MAX, x1 = -1, y1 = -1;
+    for (uint32_t i = t; i < n; i += kT) {
+        const uint32_t Y = i / a.m.W, X = i - Y * a.m.W;
+        const float v = mask_logit(p, a.m.L, a.m.S, a.m.ih, a.m.iw, a.m.H, a.m.W, Y, X);
+        inter += v > hi ? 1 : 0;
+        uni += v > lo ? 1 : 0;
+        if (v > a.thr) {
+            ++area;
+            x0 = min(x0, (int32_t)X);
+            y0 = min(y0, (int32_t)Y);
+            x1 = max(x1, (int32_t)X);
+            y1 = max(y1, (int32_t)Y);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        inter += __shfl_xor(inter, o, 64);
+        uni += __shfl_xor(uni, o, 64);
+        area += __shfl_xor(area, o, 64);
+        x0 = min(x0, __shfl_xor(x0, o, 64));
+        y0 = min(y0, __shfl_xor(y0, o, 64));
+        x1 = max(x1, __shfl_xor(x1, o, 64));
+        y1 = max(y1, __shfl_xor(y1, o, 64));
+    }
+    if ((t & 63u) == 0u) {
+        int32_t* w = sh[t >> 6];
+        w[0] = inter; w[1] = uni; w[2] = area; w[3] = x0; w[4] = y0; w[5] = x1; w[6] = y1;
+    }
+    __syncthreads();
+    if (t != 0u) return;
+    for (int w = 1; w < 4; ++w) {
+        inter += sh[w][0];
+        uni += sh[w][1];
+        area += sh[w][2];
+        x0 = min(x0, sh[w][3]);
+        y0 = min(y0, sh[w][4]);
+        x1 = max(x1, sh[w][5]);
+        y1 = max(y1, sh[w][6]);
+    }
+    if (area == 0) x0 = y0 = x1 = y1 = 0;
+    const float stab = (float)inter / (float)uni;        // 0 / 0 is NaN and fails
+    rec[kRecInter] = inter;
+    rec[kRecUnion] = uni;
+    rec[kRecArea] = area;
+    rec[kRecX0] = x0;
+    rec[kRecY0] = y0;
+    rec[kRecX1] = x1;
+    rec[kRecY1] = y1;
+    rec[kRecStab] = __float_as_int(stab);
+    rec[kRecPass] = stab >= a.stab_thresh ? 1 : 0;
+    rec[kRecIou] = __float_as_int(iou);
+}
+
+// -------------------------------------------------------- generator: NMS --
+
+// The place of every passing candidate in the order of descending score,
+// ties to the lower index: the number of passing candidates before it,
+// counted against tiles of 256 through LDS.  keep[place] = candidate.
+__global__ void __launch_bounds__(kT) k_sd_nms_rank(const int32_t* __restrict__ rec, uint32_t n,
+                                                    int32_t* __restrict__ keep) {
+    __shared__ float s_iou[kT];
+    __shared__ int32_t s_pass[kT];
+    const uint32_t t = threadIdx.x, i = blockIdx.x * kT + t;
+    const bool live = i < n && rec[(size_t)i * kRecWords + kRecPass] != 0;
+    const float mine = live ? __int_as_float(rec[(size_t)i * kRecWords + kRecIou]) : 0.0f;
+    uint32_t before = 0;
+    for (uint32_t j0 = 0; j0 < n; j0 += kT) {
+        __syncthreads();
+        const uint32_t j = j0 + t;
+        s_pass[t] = j < n ? rec[(size_t)j * kRecWords + kRecPass] : 0;
+        s_iou[t] = j < n ? __int_as_float(rec[(size_t)j * kRecWords + kRecIou]) : 0.0f;
+        __syncthreads();
+        if (live) {
+            const uint32_t m = n - j0 < kT ? n - j0 : kT;
+            for (uint32_t k = 0; k < m; ++k) {
+                const float o = s_iou[k];
+                before += s_pass[k] && (o > mine || (o == mine && j0 + k < i)) ? 1u : 0u;
+            }
+        }
+    }
+    if (live) keep[before] = (int32_t)i;
+}
+
+// torchvision's box IoU of two records' boxes, as floats.
+__device__ __forceinline__ float box_iou(const int32_t* __restrict__ a, const int32_t* __restrict__ b) {
+    const float ax0 = (float)a[kRecX0], ay0 = (float)a[kRecY0], ax1 = (float)a[kRecX1], ay1 = (float)a[kRecY1];
+    const float bx0 = (float)b[kRecX0], by0 = (float)b[kRecY0], bx1 = (float)b[kRecX1], by1 = (float)b[kRecY1];
+    const float w = fmaxf(0.0f, fminf(ax1, bx1) - fmaxf(ax0, bx0));
+    const float h = fmaxf(0.0f, fminf(ay1, by1) - fmaxf(ay0, by0));
+    const float inter = w * h, aa = (ax1 - ax0) * (ay1 - ay0), ab = (bx1 - bx0) * (by1 - by0);
+    return inter / (aa + ab - inter);
+}
+
+constexpr uint32_t kNmsMax = 3u * 64u * 64u;
+
+// The greedy pass, one workgroup: keep[0 .. m) holds the passing candidates
+// in order; candidate i of them is kept unless a kept one before it has
+// suppressed it, and a kept one marks every later one it overlaps by more
+// than the threshold (a NaN IoU marks nothing).  The kept indices are packed
+// to the front of keep in that order, the rest of its n entries set to -1.
+__global__ void __launch_bounds__(kT) k_sd_nms_greedy(const int32_t* __restrict__ rec, uint32_t n, float thresh,
+                                                      int32_t* keep, int32_t* __restrict__ count) {
+    __shared__ uint8_t gone[kNmsMax];
+    __shared__ int32_t s_m[4];
+    const uint32_t t = threadIdx.x;
+    int32_t mine = 0;
+    for (uint32_t i = t; i < n; i += kT) {
+        mine += rec[(size_t)i * kRecWords + kRecPass] != 0 ? 1 : 0;
+        gone[i] = 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if ((t & 63u) == 0u) s_m[t >> 6] = mine;
+    __syncthreads();
+    const uint32_t m = (uint32_t)(s_m[0] + s_m[1] + s_m[2] + s_m[3]);
+    // a NaN score has no place in the order and may leave an entry unwritten: such an entry is nobody
+    for (uint32_t i = t; i < m; i += kT)
+        if ((uint32_t)keep[i] >= n) gone[i] = 1;
+    __syncthreads();
+    uint32_t kept = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+        if (gone[i]) continue;                            // settled by the barrier of the sweep that set it
+        const int32_t ci = keep[i];
+        const int32_t* bi = rec + (size_t)ci * kRecWords;
+        for (uint32_t j = i + 1u + t; j < m; j += kT)
+            if (!gone[j] && box_iou(bi, rec + (size_t)keep[j] * kRecWords) > thresh) gone[j] = 1;
+        __syncthreads();                                  // the marks, and the reads of keep[j > i], are done
+        if (t == 0u) keep[kept] = ci;                     // kept <= i: no later sweep reads this entry
+        ++kept;
+    }
+    __syncthreads();
+    for (uint32_t i = kept + t; i < n; i += kT) keep[i] = -1;
+    if (t == 0u) *count = (int32_t)kept;
 }
 
 // ------------------------------------------------------------- workspace --
@@ -785,6 +1059,22 @@ struct Launcher {
         else
             k_sd_lin<16><<<dim3(div_up(maxO, 64), div_up(maxM, 16), n), kT, 0, s>>>(J);
         done("sam_decoder lin");
+    }
+    // the batched call's: the same chains, A2 / R possibly one set's rows for all (a2_mod, r_mod)
+    void lin_b(const LinJob* jobs, uint32_t n) {
+        if (rc) return;
+        LinJobs J{};
+        uint32_t maxM = 0, maxO = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            J.j[i] = jobs[i];
+            maxM = jobs[i].M > maxM ? jobs[i].M : maxM;
+            maxO = jobs[i].O > maxO ? jobs[i].O : maxO;
+        }
+        if (maxM > kMaxTok)
+            k_sd_lin<32, true><<<dim3(div_up(maxO, 64), div_up(maxM, 32), n), kT, 0, s>>>(J);
+        else
+            k_sd_lin<16, true><<<dim3(div_up(maxO, 64), div_up(maxM, 16), n), kT, 0, s>>>(J);
+        done("sam_decoder_batch lin");
     }
     void ln(const float* X, uint32_t parts, size_t stride, size_t w, size_t b, float* Y, uint32_t M) {
         if (rc) return;
@@ -938,7 +1228,7 @@ extern "C" int samnerf_sam_decoder(const void* pack, size_t pack_bytes, uint32_t
                                  run.job(W.q, nullptr, L.i2t.v, nullptr, W.tv, T)};
             run.lin(j, 3);
             if (!run.rc) {
-                k_sd_attn_img<<<dim3(div_up(N, kT), kHeads), kT, 0, s>>>(W.iq, W.tk, W.tv, W.ia, N, T);
+                k_sd_attn_img<false><<<dim3(div_up(N, kT), kHeads), kT, 0, s>>>(W.iq, W.tk, W.tv, W.ia, N, T);
                 run.done("sam_decoder image->token attention");
             }
             const LinJob o = run.job(W.ia, nullptr, L.i2t.o, W.kim, W.kx, N);
@@ -966,7 +1256,7 @@ extern "C" int samnerf_sam_decoder(const void* pack, size_t pack_bytes, uint32_t
         const LinJob up = run.job(W.kim, nullptr, l.up0, nullptr, W.u1, N);
         run.lin(&up, 1);
         if (!run.rc) {
-            k_sd_up<<<div_up(N, 16), kT, 0, s>>>(W.u1, pk + l.uplnw, pk + l.uplnb, pk + l.up1w, pk + l.up1b, W.hyp,
+            k_sd_up<false><<<div_up(N, 16), kT, 0, s>>>(W.u1, pk + l.uplnw, pk + l.uplnb, pk + l.up1w, pk + l.up1b, W.hyp,
                                                  low_res, g);
             run.done("sam_decoder upscale");
         }
@@ -987,4 +1277,262 @@ extern "C" int samnerf_sam_masks(const float* low_res, uint32_t M, uint32_t g, u
     MaskArgs a{low_res, logits, mask, 4u * g, S, in_h, in_w, H, W};
     k_sd_masks<<<dim3(div_up((uint64_t)H * W, kT), M), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
     return check_launch("sam_masks");
+}
+
+// ------------------------------------------------------------- the batch --
+
+namespace {
+
+constexpr uint32_t kMaxSets = 256;
+
+// The batched call's workspace: token-side rows [B T], image-side rows [B N];
+// what does not depend on the prompt (kim0 and layer 0's ik0, iv0, iq0) once.
+struct WorkB {
+    float *tok, *q, *x1, *tq, *tk, *tv, *ta, *ap, *hid, *part, *kim0, *ik0, *iv0, *iq0, *kim, *kx, *ik, *iv, *iq, *ia,
+        *h1, *h2, *hyp;
+    size_t bytes;
+};
+
+WorkB carve_batch(void* ws, uint32_t g, uint32_t B) {
+    WorkB w{};
+    Carver c(ws);
+    const size_t N = (size_t)g * g, BN = (size_t)B * N, tokens = (size_t)B * kMaxTok * kC;
+    w.tok = c.take(tokens);
+    w.q = c.take(tokens);
+    w.x1 = c.take(tokens);
+    w.tq = c.take(tokens);
+    w.tk = c.take(tokens);
+    w.tv = c.take(tokens);
+    w.ta = c.take(tokens);
+    w.ap = c.take((size_t)kKeySlices * B * kMaxTok * kHeads * 18);
+    w.hid = c.take((size_t)B * kMaxTok * kHid);
+    w.part = c.take(kSplit * tokens);
+    w.kim0 = c.take(N * kC);
+    w.ik0 = c.take(N * 128);
+    w.iv0 = c.take(N * 128);
+    w.iq0 = c.take(N * 128);
+    w.kim = c.take(BN * kC);
+    w.kx = c.take(BN * kC);                    // and u1, once the last norm has read it
+    w.ik = c.take(BN * 128);
+    w.iv = c.take(BN * 128);
+    w.iq = c.take(BN * 128);
+    w.ia = c.take(BN * 128);
+    w.h1 = c.take((size_t)5 * B * kC);
+    w.h2 = c.take((size_t)5 * B * kC);
+    w.hyp = c.take((size_t)4 * B * 32);
+    w.bytes = c.bytes();
+    return w;
+}
+
+bool sets_ok(uint32_t B) { return B >= 1 && B <= kMaxSets; }
+
+}  // namespace
+
+extern "C" size_t samnerf_sam_decoder_batch_workspace_size(uint32_t g, uint32_t B) {
+    return grid_ok(g) && sets_ok(B) ? carve_batch(nullptr, g, B).bytes : 0;
+}
+
+extern "C" int samnerf_sam_decoder_batch(const void* pack, size_t pack_bytes, uint32_t g, const float* features,
+                                         uint32_t h, uint32_t w, const float* points, const int32_t* labels,
+                                         uint32_t B, uint32_t P, float* low_res, float* iou, void* ws,
+                                         size_t ws_bytes, samnerf_stream_t stream) {
+    if (!grid_ok(g)) return fail(SAMNERF_EINVAL, "sam_decoder_batch: g must be a multiple of 8 in [8, 64]");
+    if (!sets_ok(B)) return fail(SAMNERF_EINVAL, "sam_decoder_batch: B must lie in [1, 256]");
+    if (P < 1 || P > kMaxP) return fail(SAMNERF_EINVAL, "sam_decoder_batch: P must lie in [1, 58]");
+    if (!pack || !features || !points || !labels || !low_res || !iou)
+        return fail(SAMNERF_EINVAL, "sam_decoder_batch: null pack / features / points / labels / low_res / iou");
+    if (!ws) return fail(SAMNERF_EINVAL, "sam_decoder_batch: null workspace");
+    if ((h == 0) != (w == 0) || h > 1024 || w > 1024)
+        return fail(SAMNERF_EINVAL,
+                    "sam_decoder_batch: h and w are both 0 (features [g*g][256]) or both in [1, 1024]");
+    if (!aligned16(pack) || !aligned16(ws) || !aligned16(iou))
+        return fail(SAMNERF_EINVAL, "sam_decoder_batch: pack, iou and workspace must be 16-byte aligned");
+    const Layout l = make_layout(g);
+    if (pack_bytes < l.pack_count * sizeof(float))
+        return fail(SAMNERF_EINVAL, "sam_decoder_batch: pack of %zu bytes, %zu expected for g = %u", pack_bytes,
+                    l.pack_count * sizeof(float), g);
+    const WorkB W = carve_batch(ws, g, B);
+    if (ws_bytes < W.bytes)
+        return fail(SAMNERF_EWORKSPACE, "sam_decoder_batch: workspace of %zu bytes, %zu needed", ws_bytes, W.bytes);
+    const float* pk = static_cast<const float*>(pack);
+    const uint32_t N = g * g, T = P + 6u, BT = B * T, BN = B * N;
+    Launcher run{reinterpret_cast<hipStream_t>(stream), pk};
+    hipStream_t s = run.s;
+
+    SrcArgs sa{features, pk + l.nomask, W.kim0, g, h, w, 0, 0};
+    if (h) {
+        const double r = w > h ? (double)g / w : (double)g / h;
+        sa.vh = (uint32_t)(int)(h * r);
+        sa.vw = (uint32_t)(int)(w * r);
+        if (sa.vh < 1 || sa.vw < 1 || sa.vh > g || sa.vw > g)
+            return fail(SAMNERF_EINVAL, "sam_decoder_batch: a %u x %u map resizes to %u x %u", h, w, sa.vh, sa.vw);
+    }
+    k_sd_src<<<div_up(N, 4), kT, 0, s>>>(sa);
+    run.done("sam_decoder_batch src");
+    k_sd_tokens_batch<<<BT, kT, 0, s>>>(pk, l.G, l.pt[0], l.pt[1], l.nap, l.iou, l.mtok, points, labels, W.tok, W.q, P,
+                                        16u * g);
+    run.done("sam_decoder_batch tokens");
+
+    const float* ipe = pk + l.ipe;
+    const size_t tokens = (size_t)BT * kC;
+    // a job whose A2 (image_pe) or R is one set's N rows, read by every set
+    auto wide = [&](LinJob j, uint32_t a2_mod, uint32_t r_mod) {
+        j.a2_mod = a2_mod;
+        j.r_mod = r_mod;
+        return j;
+    };
+    // token -> image attention of `a`; first: the image tokens are still the call's, one k / v for every set
+    auto token_to_image = [&](const Attn& a, size_t nw, size_t nb, bool first) {
+        const LinJob j[3] = {
+            run.job(W.q, W.tok, a.q, nullptr, W.tq, BT),
+            first ? run.job(W.kim0, ipe, a.k, nullptr, W.ik0, N)
+                  : wide(run.job(W.kim, ipe, a.k, nullptr, W.ik, BN), N, 0),
+            first ? run.job(W.kim0, nullptr, a.v, nullptr, W.iv0, N) : run.job(W.kim, nullptr, a.v, nullptr, W.iv, BN)};
+        run.lin_b(j, 3);
+        if (!run.rc) {
+            k_sd_attn_tok<16, 2, 4, true><<<dim3(B * div_up(T, 2), kHeads, kKeySlices), kT, 0, s>>>(
+                W.tq, first ? W.ik0 : W.ik, first ? W.iv0 : W.iv, W.ta, W.ap, T, N, B, first ? 0 : (size_t)N * 128);
+            run.done("sam_decoder_batch token->image attention");
+        }
+        if (!run.rc) {
+            k_sd_attn_merge<<<BT, 128, 0, s>>>(W.ap, W.ta, BT, kKeySlices);
+            run.done("sam_decoder_batch attention merge");
+        }
+        const LinJob o = run.job(W.ta, nullptr, a.o, W.q, W.x1, BT);
+        run.lin_b(&o, 1);
+        run.ln(W.x1, 1, 0, nw, nb, W.q, BT);
+    };
+    for (int li = 0; li < 2; ++li) {
+        const Layer& L = l.L[li];
+        const float* qpe = li ? W.tok : nullptr;
+        {
+            const LinJob j[3] = {run.job(W.q, qpe, L.self.q, nullptr, W.tq, BT),
+                                 run.job(W.q, qpe, L.self.k, nullptr, W.tk, BT),
+                                 run.job(W.q, nullptr, L.self.v, nullptr, W.tv, BT)};
+            run.lin_b(j, 3);
+            if (!run.rc) {
+                k_sd_attn_tok<32, 1, 1, true><<<dim3(BT, kHeads), kT, 0, s>>>(W.tq, W.tk, W.tv, W.ta, nullptr, T, T, B,
+                                                                              (size_t)T * kC);
+                run.done("sam_decoder_batch self attention");
+            }
+            const LinJob o = run.job(W.ta, nullptr, L.self.o, li ? W.q : nullptr, W.x1, BT);
+            run.lin_b(&o, 1);
+            run.ln(W.x1, 1, 0, L.nw[0], L.nb[0], W.q, BT);
+        }
+        token_to_image(L.t2i, L.nw[1], L.nb[1], li == 0);
+        {
+            const LinJob up = run.job(W.q, nullptr, L.lin1, nullptr, W.hid, BT, true);
+            run.lin_b(&up, 1);
+            LinJob j[kSplit];
+            for (uint32_t k = 0; k < kSplit; ++k) {
+                const uint32_t k0 = k * (kHid / kSplit);
+                j[k] = {W.hid + k0, nullptr, pk + L.lin2.w + (size_t)k0 * kC, k ? nullptr : pk + L.lin2.b,
+                        k ? nullptr : W.q, W.part + k * tokens, BT, kHid / kSplit, kC, kHid, 0u};
+            }
+            run.lin_b(j, kSplit);
+            run.ln(W.part, kSplit, tokens, L.nw[2], L.nb[2], W.q, BT);
+        }
+        {
+            const bool first = li == 0;
+            const LinJob j[3] = {first ? run.job(W.kim0, ipe, L.i2t.q, nullptr, W.iq0, N)
+                                       : wide(run.job(W.kim, ipe, L.i2t.q, nullptr, W.iq, BN), N, 0),
+                                 run.job(W.q, W.tok, L.i2t.k, nullptr, W.tk, BT),
+                                 run.job(W.q, nullptr, L.i2t.v, nullptr, W.tv, BT)};
+            run.lin_b(j, 3);
+            if (!run.rc) {
+                k_sd_attn_img<true><<<dim3(div_up(N, kT), kHeads, B), kT, 0, s>>>(
+                    first ? W.iq0 : W.iq, W.tk, W.tv, W.ia, N, T, first ? 0 : (size_t)N * 128);
+                run.done("sam_decoder_batch image->token attention");
+            }
+            const LinJob o = first ? wide(run.job(W.ia, nullptr, L.i2t.o, W.kim0, W.kx, BN), 0, N)
+                                   : run.job(W.ia, nullptr, L.i2t.o, W.kim, W.kx, BN);
+            run.lin_b(&o, 1);
+            run.ln(W.kx, 1, 0, L.nw[3], L.nb[3], W.kim, BN);
+        }
+    }
+    token_to_image(l.fin, l.nfw, l.nfb, false);
+    // the hypernetwork MLPs and the IoU head: job i takes token row (i < 4 ? 1 + i : 0) of every set
+    {
+        LinJob j[5];
+        for (uint32_t i = 0; i < 5; ++i) {
+            j[i] = run.job(W.q + (size_t)(i < 4 ? 1 + i : 0) * kC, nullptr, i < 4 ? l.hyp[i][0] : l.iouh[0], nullptr,
+                           W.h1 + (size_t)i * B * kC, B, true);
+            j[i].lda = T * kC;
+        }
+        run.lin_b(j, 5);
+        for (uint32_t i = 0; i < 5; ++i)
+            j[i] = run.job(W.h1 + (size_t)i * B * kC, nullptr, i < 4 ? l.hyp[i][1] : l.iouh[1], nullptr,
+                           W.h2 + (size_t)i * B * kC, B, true);
+        run.lin_b(j, 5);
+        for (uint32_t i = 0; i < 5; ++i)
+            j[i] = run.job(W.h2 + (size_t)i * B * kC, nullptr, i < 4 ? l.hyp[i][2] : l.iouh[2], nullptr,
+                           i < 4 ? W.hyp + (size_t)i * B * 32 : iou, B);
+        run.lin_b(j, 5);
+    }
+    {
+        float* u1 = W.kx;
+        const LinJob up = run.job(W.kim, nullptr, l.up0, nullptr, u1, BN);
+        run.lin_b(&up, 1);
+        if (!run.rc) {
+            k_sd_up<true><<<dim3(div_up(N, 16), B), kT, 0, s>>>(u1, pk + l.uplnw, pk + l.uplnb, pk + l.up1w,
+                                                                pk + l.up1b, W.hyp, low_res, g);
+            run.done("sam_decoder_batch upscale");
+        }
+    }
+    if (!run.rc) g_launches.store(run.count);
+    return run.rc;
+}
+
+// ---------------------------------------------------------- the generator --
+
+namespace {
+
+const char* view_bad(uint32_t g, uint32_t in_h, uint32_t in_w, uint32_t H, uint32_t W) {
+    if (!grid_ok(g)) return "g must be a multiple of 8 in [8, 64]";
+    if (in_h < 1 || in_w < 1 || in_h > 16u * g || in_w > 16u * g) return "input_size must lie in [1, 16 g]";
+    if (H < 1 || W < 1 || H > 8192 || W > 8192) return "H and W must lie in [1, 8192]";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int samnerf_sam_masks_select(const float* low_res, uint32_t n, const int32_t* index, uint32_t count,
+                                        const int32_t* count_dev, uint32_t g, uint32_t in_h, uint32_t in_w, uint32_t H,
+                                        uint32_t W, float mask_threshold, float* logits, uint8_t* mask,
+                                        samnerf_stream_t stream) {
+    if (const char* why = view_bad(g, in_h, in_w, H, W)) return fail(SAMNERF_EINVAL, "sam_masks_select: %s", why);
+    if (!low_res || (!logits && !mask)) return fail(SAMNERF_EINVAL, "sam_masks_select: null low_res, or no output");
+    if (n < 1 || n > kNmsMax) return fail(SAMNERF_EINVAL, "sam_masks_select: n must lie in [1, %u]", kNmsMax);
+    if (count > kNmsMax || (!index && count > n))
+        return fail(SAMNERF_EINVAL, "sam_masks_select: a count of %u over a table of %u", count, n);
+    if (count == 0) return SAMNERF_OK;
+    SelectArgs a{{low_res, logits, mask, 4u * g, 16u * g, in_h, in_w, H, W}, index, count_dev, n, mask_threshold};
+    k_sd_masks_select<<<dim3(div_up((uint64_t)H * W, kT), count), kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
+    return check_launch("sam_masks_select");
+}
+
+extern "C" int samnerf_sam_mask_stats(const float* low_res, const float* iou, uint32_t n, uint32_t g, uint32_t in_h,
+                                      uint32_t in_w, uint32_t H, uint32_t W, float pred_iou_thresh,
+                                      float mask_threshold, float stability_score_offset,
+                                      float stability_score_thresh, int32_t* records, samnerf_stream_t stream) {
+    if (const char* why = view_bad(g, in_h, in_w, H, W)) return fail(SAMNERF_EINVAL, "sam_mask_stats: %s", why);
+    if (n > kNmsMax) return fail(SAMNERF_EINVAL, "sam_mask_stats: n must not exceed %u", kNmsMax);
+    if (n == 0) return SAMNERF_OK;
+    if (!low_res || !iou || !records) return fail(SAMNERF_EINVAL, "sam_mask_stats: null low_res / iou / records");
+    StatsArgs a{{low_res, nullptr, nullptr, 4u * g, 16u * g, in_h, in_w, H, W}, iou, records, pred_iou_thresh,
+                mask_threshold, stability_score_offset, stability_score_thresh};
+    k_sd_mask_stats<<<n, kT, 0, reinterpret_cast<hipStream_t>(stream)>>>(a);
+    return check_launch("sam_mask_stats");
+}
+
+extern "C" int samnerf_sam_nms(const int32_t* records, uint32_t n, float box_nms_thresh, int32_t* keep,
+                               int32_t* count, samnerf_stream_t stream) {
+    if (n > kNmsMax) return fail(SAMNERF_EINVAL, "sam_nms: n must not exceed %u", kNmsMax);
+    if (n == 0) return SAMNERF_OK;
+    if (!records || !keep || !count) return fail(SAMNERF_EINVAL, "sam_nms: null records / keep / count");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    k_sd_nms_rank<<<div_up(n, kT), kT, 0, s>>>(records, n, keep);
+    if (int rc = check_launch("sam_nms rank")) return rc;
+    k_sd_nms_greedy<<<1, kT, 0, s>>>(records, n, box_nms_thresh, keep, count);
+    return check_launch("sam_nms greedy");
 }

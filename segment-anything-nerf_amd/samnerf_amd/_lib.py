@@ -206,6 +206,14 @@ _SIGS = {
                              ctypes.POINTER(ctypes.c_int32), _u32, _vp, _vp, _vp, _sz, _vp], _int),
     "samnerf_sam_decoder_launches": ([], _int),
     "samnerf_sam_masks": ([_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp], _int),
+    "samnerf_sam_decoder_batch_workspace_size": ([_u32, _u32], _sz),
+    "samnerf_sam_decoder_batch": ([_vp, _sz, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp],
+                                  _int),
+    "samnerf_sam_masks_select": ([_vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _f32, _vp, _vp, _vp],
+                                 _int),
+    "samnerf_sam_mask_stats": ([_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
+                               _int),
+    "samnerf_sam_nms": ([_vp, _u32, _f32, _vp, _vp, _vp], _int),
 }
 
 

@@ -101,6 +101,24 @@ def sam_predict_device(decoder, H, W, samvit_hwc, point_coords=None, rng=None):
     return masks, (pts / r).astype(np.int32), low_res[:1]
 
 
+def segment_everything(decoder_or_generator, H, W, samvit_hwc, **kw):
+    """SAM's automatic mask generator on a rendered view (debug.py's
+    Auto_Generator with `feature=`, batch_generate_mask.py's per-view masks):
+    samvit_hwc [h, w, 256] goes to the decoder as it is, like
+    sam_predict_device.  A sam_decoder.SamDecoder is wrapped in a
+    sam_generator.DeviceMaskGenerator built from the generator's keywords
+    (points_per_side, pred_iou_thresh, ...); `multimask_output` and
+    `as_tensors` go to generate()."""
+    from .sam_generator import DeviceMaskGenerator
+    call = {k: kw.pop(k) for k in ("multimask_output", "as_tensors") if k in kw}
+    gen = decoder_or_generator
+    if not isinstance(gen, DeviceMaskGenerator):
+        gen = DeviceMaskGenerator(gen, **kw)
+    elif kw:
+        raise TypeError(f"segment_everything: {sorted(kw)} belong to the generator's constructor")
+    return gen.generate(samvit_hwc.contiguous(), H, W, **call)
+
+
 class PromptMemory:
     """The remembered 3D prompt points of Trainer.test_step (utils.py:1318-1384),
     which make a click follow its object across views: a click is lifted to 3D

@@ -6,6 +6,10 @@
 mask-input `mask_downscaling.*` keys are ignored) and packs it once.
 `decode` turns image tokens and clicks into the four low-res masks and IoU
 scores in 44 launches; `masks` is Sam.postprocess_masks in one.
+`decode_batch` takes B prompt sets of P points each (device tensors, B up to
+256) in the same 44 launches, every set with the bits of its own `decode`;
+`masks_select`, `mask_stats` and `nms` are the automatic mask generator's
+steps on the device (sam_generator.DeviceMaskGenerator puts them together).
 `DevicePredictor` gives them SamPredictor's interface, so
 `sam_bridge.sam_predict` / `render_and_predict` drive it unchanged.
 
@@ -14,9 +18,10 @@ project's own float64 restatement (tests/sam_decoder_ref.py) with synthetic
 weights.  It has not been compared with an installed segment_anything or a
 real checkpoint.
 
-Not built, each raising NotImplementedError: a mask input, box prompts, more
-than one prompt set a call (the automatic mask generator's batches), the HQ
-token (`interm_features`), and the ViT image encoder.
+Not built, each raising NotImplementedError: a mask input, box prompts,
+prompt sets of different sizes in one call, the HQ token (`interm_features`),
+and the ViT image encoder.  `DevicePredictor.predict_torch` keeps SamPredictor's
+one-set form; `predict_points_batch` is the batched one.
 """
 import ctypes
 
@@ -27,6 +32,9 @@ from .ops import _ptr, _stream
 
 C = 256
 MAX_POINTS = 58
+MAX_SETS = 256
+MAX_CANDIDATES = 3 * 64 * 64
+REC_WORDS = 10        # SAMNERF_SAM_REC_WORDS: inter, union, area, x0, y0, x1, y1, stability, pass, iou
 
 
 def _attention(prefix, inner):
@@ -153,6 +161,117 @@ class SamDecoder:
               "sam_decoder")
         return low, iou
 
+    def _features_hw(self, features, who):
+        g = self.g
+        if not (features.is_cuda and features.dtype == torch.float32 and features.is_contiguous()):
+            raise ValueError(f"SamDecoder.{who}: features must be a contiguous fp32 tensor on the device")
+        if features.dim() == 2 and tuple(features.shape) == (g * g, C):
+            return 0, 0
+        if features.dim() == 3 and features.shape[2] == C:
+            return int(features.shape[0]), int(features.shape[1])
+        raise ValueError(f"SamDecoder.{who}: features must be [{g * g}, {C}] or [h, w, {C}], "
+                         f"not {tuple(features.shape)}")
+
+    def _batch_workspace(self, B):
+        from ._lib import lib
+        need = lib().samnerf_sam_decoder_batch_workspace_size(self.g, B)
+        if need == 0:
+            raise ValueError(f"SamDecoder.decode_batch: B = {B} must lie in [1, {MAX_SETS}]")
+        ws = getattr(self, "_ws_batch", None)
+        if ws is None or ws.numel() < need:
+            self._ws_batch = ws = None                         # the old one goes before the new one comes
+            self._ws_batch = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws, need
+
+    def decode_batch(self, features, points, labels=None, out=None, workspace=None):
+        """B prompt sets over one image: features as in `decode`; points
+        [B, P, 2] (x, y) in the S frame, fractional or whole, and labels [B, P]
+        (default all 1), as device tensors (used as they are: no host copy) or
+        host arrays (labels then checked to be 0 / 1).  Returns (low_res
+        [B, 4, 4g, 4g], iou [B, 4]); set b has the bits of decode(points[b]).
+        `out` = (low_res, iou) and `workspace` (a uint8 device tensor of
+        samnerf_sam_decoder_batch_workspace_size bytes) may be given."""
+        from ._lib import check, lib
+        g = self.g
+        h, w = self._features_hw(features, "decode_batch")
+        if not torch.is_tensor(points):
+            points = torch.as_tensor(np.asarray(points, dtype=np.float32))
+        if points.dim() != 3 or points.shape[2] != 2:
+            raise ValueError(f"SamDecoder.decode_batch: points must be [B, P, 2], not {tuple(points.shape)}")
+        B, P = int(points.shape[0]), int(points.shape[1])
+        if not 1 <= P <= MAX_POINTS:
+            raise ValueError(f"SamDecoder.decode_batch: P = {P} must lie in [1, {MAX_POINTS}]")
+        points = points.to(device=self.device, dtype=torch.float32).contiguous()
+        if labels is None:
+            labels = torch.ones(B, P, dtype=torch.int32, device=self.device)
+        else:
+            if not (torch.is_tensor(labels) and labels.is_cuda):
+                host = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
+                if not np.isin(host, (0, 1)).all():
+                    raise ValueError("SamDecoder.decode_batch: labels must be 0 or 1")
+                labels = torch.as_tensor(host.astype(np.int32))
+            labels = labels.to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(labels.shape) != (B, P):
+            raise ValueError(f"SamDecoder.decode_batch: labels must be [{B}, {P}], not {tuple(labels.shape)}")
+        if workspace is None:
+            workspace, need = self._batch_workspace(B)
+        else:
+            need = workspace.numel()
+        low, iou = out if out is not None else (torch.empty(B, 4, 4 * g, 4 * g, device=self.device),
+                                                torch.empty(B, 4, device=self.device))
+        check(lib().samnerf_sam_decoder_batch(_ptr(self.pack), self.pack.numel(), g, _ptr(features), h, w,
+                                              _ptr(points), _ptr(labels), B, P, _ptr(low), _ptr(iou),
+                                              _ptr(workspace), need, _stream(self.device)), "sam_decoder_batch")
+        return low, iou
+
+    def masks_select(self, low_res, input_size, original_size, index=None, count=None, cap=None, logits=False,
+                     out=None, mask_threshold=0.0):
+        """`masks` as a gather: slot s of the output is mask index[s] (a device
+        int32 tensor; None: s) of the table low_res [n, 4g, 4g].  `cap` slots
+        (default: len(index), or n) are launched; `count`, a device int32, keeps
+        the slots at and past it as they were.  mask = logit > mask_threshold."""
+        from ._lib import check, lib
+        low_res = low_res.contiguous()
+        n, (H, W) = int(low_res.shape[0]), (int(original_size[0]), int(original_size[1]))
+        if cap is None:
+            cap = n if index is None else int(index.numel())
+        if out is None:
+            out = torch.zeros(cap, H, W, device=low_res.device, dtype=torch.float32 if logits else torch.uint8)
+        check(lib().samnerf_sam_masks_select(_ptr(low_res), n, None if index is None else _ptr(index), cap,
+                                             None if count is None else _ptr(count), self.g, int(input_size[0]),
+                                             int(input_size[1]), H, W, float(mask_threshold),
+                                             _ptr(out) if logits else None, None if logits else _ptr(out),
+                                             _stream(low_res)), "sam_masks_select")
+        return out if logits else out.view(torch.bool)
+
+    def mask_stats(self, low_res, iou, input_size, original_size, pred_iou_thresh, stability_score_thresh,
+                   stability_score_offset=1.0, mask_threshold=0.0, out=None):
+        """The generator's filters of n candidates (low_res [n, 4g, 4g], iou
+        [n]) over the (H, W) view: int32 records [n, REC_WORDS] (the stability
+        and iou words hold fp32 bits), include/samnerf_hip.h."""
+        from ._lib import check, lib
+        low_res, iou = low_res.contiguous(), iou.contiguous()
+        n = int(low_res.shape[0])
+        if out is None:
+            out = torch.empty(n, REC_WORDS, dtype=torch.int32, device=low_res.device)
+        check(lib().samnerf_sam_mask_stats(_ptr(low_res), _ptr(iou), n, self.g, int(input_size[0]),
+                                           int(input_size[1]), int(original_size[0]), int(original_size[1]),
+                                           float(pred_iou_thresh), float(mask_threshold),
+                                           float(stability_score_offset), float(stability_score_thresh), _ptr(out),
+                                           _stream(low_res)), "sam_mask_stats")
+        return out
+
+    def nms(self, records, box_nms_thresh, out=None):
+        """Greedy box NMS of the passing records on the device: (keep [n] int32,
+        the kept candidate indices in order and then -1; count [1] int32)."""
+        from ._lib import check, lib
+        n = int(records.shape[0])
+        keep, count = out if out is not None else (torch.full((n,), -1, dtype=torch.int32, device=records.device),
+                                                   torch.zeros(1, dtype=torch.int32, device=records.device))
+        check(lib().samnerf_sam_nms(_ptr(records), n, float(box_nms_thresh), _ptr(keep), _ptr(count),
+                                    _stream(records)), "sam_nms")
+        return keep, count
+
     def masks(self, low_res, input_size, original_size, logits=False, out=None):
         """Sam.postprocess_masks and the threshold: low_res [M, 4g, 4g] ->
         bool masks [M, H, W] (logits=False) or their fp32 logits."""
@@ -210,6 +329,9 @@ class DevicePredictor:
 
     def predict_torch(self, point_coords, point_labels, boxes=None, mask_input=None, multimask_output=True,
                       return_logits=False, hq_token_only=False):
+        """SamPredictor.predict_torch for one prompt set (B = 1) of whole-pixel
+        points.  More than one set is refused here, as it always was;
+        `predict_points_batch` takes B sets."""
         if not self.is_image_set or self._tokens is None:
             raise RuntimeError("DevicePredictor: an image's features must be set before a prediction")
         if mask_input is not None:
@@ -231,3 +353,22 @@ class DevicePredictor:
         low, iou = low[sel], iou[sel]
         masks = self.decoder.masks(low, self.input_size, self.original_size, logits=return_logits)
         return masks[None], iou[None], low[None]
+
+    def predict_points_batch(self, point_coords, point_labels, multimask_output=True, return_logits=False):
+        """predict_torch for B prompt sets of P points each: point_coords
+        [B, P, 2] in the input frame (fractional allowed), point_labels [B, P];
+        tensors on the device stay there.  Returns (masks [B, M, H, W] bool or
+        logits, iou [B, M], low_res [B, M, 4g, 4g]), M = 3 (masks 1 .. 3) with
+        multimask_output and 1 (mask 0) without."""
+        if not self.is_image_set or self._tokens is None:
+            raise RuntimeError("DevicePredictor: an image's features must be set before a prediction")
+        if self.interm_features is not None:
+            raise NotImplementedError("DevicePredictor: the HQ token (interm_features) is not built; plain SAM only")
+        dec = self.decoder
+        low, iou = dec.decode_batch(self._tokens, point_coords, point_labels)
+        sel = slice(1, 4) if multimask_output else slice(0, 1)
+        low, iou = low[:, sel].contiguous(), iou[:, sel].contiguous()
+        B, M, L = low.shape[0], low.shape[1], low.shape[2]
+        H, W = int(self.original_size[0]), int(self.original_size[1])
+        masks = dec.masks_select(low.view(B * M, L, L), self.input_size, (H, W), logits=return_logits)
+        return masks.view(B, M, H, W), iou, low
